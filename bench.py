@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- encode+decode frames/s of the MI355X VidTok path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dtype bf16|fp32|bf16x3] [--batch B] [--no-graph]
+    python bench.py --gpus N --steps K --warmup W [--dtype bf16|fp32|bf16x3] [--batch B] [--no-graph] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit, higher_is_better, dtype,
+ms_per_step (and the run's configuration).  Everything else below -- the other noise source, the roofline, traffic,
+other modes and configurations, the CPU baseline -- runs only with --full (--breakdown runs the roofline leg it prints
+from).  --dump-outputs DIR writes what the last timed step returned (z, dec and the regularizer's log tensors) as
+DIR/<name>.npy in float32; inputs, weights and the KL noise stream are seeded, so two builds compare output for output.
 
 One "step" = one pass of the hot path, `model(x)` = encode -> KL regularizer -> decode
 (reference AutoencodingEngine.forward, vidtok/models/autoencoder.py:221-229), over one batch of
@@ -404,6 +410,34 @@ def selftest_host_loop(steps, batch, world):
     return dt
 
 
+DUMP_LIMIT_BYTES = 64_000_000        # all files together, .npy headers included
+DUMP_WHOLE_ELEMENTS = 2 ** 20      # arrays up to this size are always written whole
+
+
+def dump_outputs(out, dirname, seed=0):
+    """--dump-outputs: the arrays a caller of the timed step receives -- z (the latent), dec (the reconstruction) and every
+    tensor of the regularizer's log -- as <dirname>/<name>.npy in float32, 64 MB at most in all.  Beyond that budget each
+    large array is written as a fixed sample of its elements (flattened, seeded indices in ascending order), the same
+    sample for the same arguments."""
+    import numpy as np
+
+    z, dec, log = out
+    arrays = {"z": z, "dec": dec, **{f"log_{k}": v for k, v in sorted(log.items()) if torch.is_tensor(v)}}
+    arrays = {k: v.detach().float().cpu().contiguous() for k, v in arrays.items()}
+    budget = (DUMP_LIMIT_BYTES - 2 ** 20) // 4      # float32 elements; 1 MiB left for the headers
+    small = sum(v.numel() for v in arrays.values() if v.numel() <= DUMP_WHOLE_ELEMENTS)
+    large = sum(v.numel() for v in arrays.values() if v.numel() > DUMP_WHOLE_ELEMENTS)
+    os.makedirs(dirname, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+    for name, v in arrays.items():
+        if small + large > budget and v.numel() > DUMP_WHOLE_ELEMENTS:
+            k = v.numel() * (budget - small) // large
+            idx = torch.randint(v.numel(), (k,), generator=g).sort().values
+            print(f"[bench] {name}: {k} of {v.numel()} elements written (seeded sample, {DUMP_LIMIT_BYTES // 10 ** 6} MB budget)", file=sys.stderr)
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), v.numpy())
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` outside a launcher: re-execute under torch.distributed.run, one rank per GPU."""
     import socket
@@ -448,8 +482,16 @@ def main():
                          "fill, encoder replay, KL regularizer with the host noise draw, decoder replay, output clone) with the GPU work stubbed, "
                          "and report the max-over-ranks host time per step")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the N = 1 extras of the line: the other arithmetic modes (parity_mode, modes) and BASELINE configs[2] / [4]")
+                    help="with --full: skip the N = 1 extras of the line: the other arithmetic modes (parity_mode, modes) and BASELINE configs[2] / [4]")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything the headline figure does not need: the other noise source, the "
+                         "roofline (kernel-only replays, HBM classes, PMC traffic), the other modes and configurations, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (z, dec, the regularizer's log tensors) as DIR/<name>.npy in float32, "
+                         "64 MB at most (rank 0's shard when N > 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if not torch.cuda.is_available() and not args.selftest_spawn:
         raise SystemExit("bench.py needs a GPU: the vidtok_amd path has no CPU fallback")
@@ -535,6 +577,7 @@ def main():
     # launch mode: the engine's own per-shape hipGraph cache (vidtok_amd/graphs.py: encoder and decoder launch
     # sequences captured on their second call, replayed afterwards); --no-graph launches every kernel eagerly
     model.enable_graphs(not args.no_graph)
+    torch.manual_seed(77 + rank)   # the KL noise stream (host generator, or device philox with --noise device): same arguments, same outputs
     for _ in range(max(3, args.warmup)):
         out = step()
     torch.cuda.synchronize()
@@ -556,13 +599,15 @@ def main():
     # one tiny RCCL all_reduce; "ranks": every rank contributes 1 -- the sum is the number of ranks the collective really reached
     red = reduce_metrics(elapsed, {"frames": float(B * T_REAL * args.steps), "ranks": 1.0}, device=dev)
     elapsed, total_frames = red["elapsed_s"], red["frames"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
     # the same K steps with the OTHER noise source (host stream vs device philox), so the line shows what the reference's
     # host-side noise protocol costs per step (per rank: it is the host cost SURVEY.md section 8e names as the 8-GPU risk)
     other_noise = "device" if args.noise == "host" else "host"
     noise_rec = {"timed": args.noise, f"ms_per_step_{args.noise}": round(elapsed / args.steps * 1e3, 3), "host_threads_per_rank": torch.get_num_threads(),
                  "note": "host = one torch.randn(shape) of the CPU generator per step (the reference's stream, distributions.py:16-18), pinned "
                          "double buffer + async upload; device = ATen philox kernel"}
-    if not args.no_extras:       # (--no-extras, the profiled form of the command, launches nothing but the timed step's kernels)
+    if args.full and not args.no_extras:       # (--no-extras, the profiled form of the command, launches nothing but the timed step's kernels)
         model.regularization.noise_source = other_noise
         for _ in range(2):
             run()
@@ -585,7 +630,7 @@ def main():
 
     # ---- roofline leg: the conv launches of one step, replayed alone from a hipGraph, timed with HIP events -----
     roof = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.breakdown):
         model.enable_graphs(False)
         ops.CONV_RECORD, ops.LN_RECORD = [], []
         step()                                          # eager: records descriptors + keeps their tensors alive
@@ -709,7 +754,7 @@ def main():
     # HBM-side bytes per launch: PMC counters cannot be read inside an un-profiled process, so two rocprofv3 passes over
     # a child run of this command measure them now; the committed pass of profiles/ is the fallback (and what
     # --traffic profile quotes)
-    extras_on = world == 1 and not args.no_extras
+    extras_on = args.full and world == 1 and not args.no_extras
     modes = others = None
     extras_error = None
     if extras_on:
@@ -719,7 +764,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             extras_error = f"{type(e).__name__}: {e}"
             print(f"[bench] extras failed: {extras_error}", file=sys.stderr)
-    if args.traffic == "pmc":
+    if roof is not None and args.traffic == "pmc":
         del model, out, z, dec
         torch.cuda.empty_cache()
         ttab = [] if args.breakdown else None
@@ -736,13 +781,13 @@ def main():
                       f"{sum(g['algorithmic'] for g in ttab) / 1e9:.1f} GB per step", file=sys.stderr)
         else:
             roof["traffic_source"] = f"live measurement failed: {src}"
-    if roof["traffic"] is None and args.traffic != "none":
+    if roof is not None and roof["traffic"] is None and args.traffic != "none":
         tb, src = committed_traffic(args.dtype, B)
         if tb is not None:
             roof["traffic"] = tb
             roof["traffic_source"] = src + ("" if args.traffic == "profile" else f"; {roof['traffic_source']}")
 
-    cpu, ref = (None, None) if args.no_cpu_baseline else cpu_baseline(config, clip0)
+    cpu, ref = (None, None) if args.no_cpu_baseline or not args.full else cpu_baseline(config, clip0)
     parity_mode = mode_table = None
     if modes is not None:
         # every arithmetic mode on the bench workload: frames/s, and the distance of its output for clip 0 from the CPU
@@ -772,7 +817,7 @@ def main():
                    "global_batch": world * B, "parallelism": f"dp{world} (batch-sharded, no data-path collective; ranks_seen = the world size the RCCL "
                                                               f"metrics all_reduce counted)",
                    "launch": "hipGraph replay (engine graph cache)" if graph is not None else "eager"},
-        "output_finite": ok, "noise": noise_rec, "roofline": roof, "cpu_baseline": cpu,
+        "full": args.full, "output_finite": ok, "noise": noise_rec, "roofline": roof, "cpu_baseline": cpu,
     }
     if parity_mode is not None:
         line["parity_mode"], line["modes"], line["other_configs"] = parity_mode, mode_table, others

@@ -272,6 +272,39 @@ def test_bench_committed_traffic_fallback(tmp_path, monkeypatch):
     assert bench.committed_traffic("fp32", 4)[0] is None
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: every array of the step's result as float32 .npy, 64 MB at most in all; the benchmark's own
+    size is written whole, a larger batch as the same seeded sample on every run"""
+    import sys
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def total(d):
+        return sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
+
+    g = torch.Generator().manual_seed(0)
+    z = torch.randn((4, 4, 5, 32, 32), generator=g).bfloat16()
+    dec = torch.randn((4, 3, 17, 256, 256), generator=g).bfloat16()          # B = 4: what a plain run returns
+    bench.dump_outputs((z, dec, {"kl_loss": torch.tensor(0.25), "note": "not a tensor"}), str(tmp_path / "b4"))
+    assert sorted(os.listdir(tmp_path / "b4")) == ["dec.npy", "log_kl_loss.npy", "z.npy"]
+    got = np.load(tmp_path / "b4" / "dec.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, dec.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "b4" / "z.npy"), z.float().numpy()) and np.load(tmp_path / "b4" / "log_kl_loss.npy") == 0.25
+    assert total(tmp_path / "b4") <= bench.DUMP_LIMIT_BYTES
+    dec8 = torch.randn((8, 3, 17, 256, 256), generator=g)                   # too large: a sample, under the budget, reproducible
+    for d in ("b8a", "b8b"):
+        bench.dump_outputs((z, dec8, {}), str(tmp_path / d))
+        assert total(tmp_path / d) <= bench.DUMP_LIMIT_BYTES
+    a, b = np.load(tmp_path / "b8a" / "dec.npy"), np.load(tmp_path / "b8b" / "dec.npy")
+    assert a.dtype == np.float32 and a.size > dec8.numel() // 2 and np.array_equal(a, b)
+    assert np.isin(a[:1000], dec8.numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "b8a" / "z.npy"), z.float().numpy())
+
+
 def test_model_handle_without_gpu(built_lib):
     """The handle-level C-ABI (csrc/model.cpp) up to the first launch: config validation, the struct mirror, the list of
     reference state_dict keys the C++ stage graph reads (= the encoder / decoder keys of the Python model), latent

@@ -567,6 +567,51 @@ int64_t vt_eval_work_floats(int32_t B, int32_t T);
 int vt_eval_psnr_ssim(const float* x, const float* y, float* psnr, float* ssim, float* work, int32_t B, int32_t C,
                       int32_t T, int32_t H, int32_t W, int32_t raw, vt_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LPIPS, the third metric of the reference's eval loop (scripts/inference_evaluate.py:164-186), on VGG16 features
+ * (vidtok/modules/lpips.py).  Per image pair n of N:
+ *   ScalingLayer  (v - shift) / scale, shift = [-0.030, -0.088, -0.188], scale = [0.458, 0.448, 0.450]   lpips.py:98-105
+ *   vgg16         features[0:30]: 3x3 conv s1 p1 + bias + ReLU, MaxPool2d(2, 2) (floor) at 4, 9, 16, 23;
+ *                 taps relu1_2 (64 ch), relu2_2 (128, /2), relu3_3 (256, /4), relu4_3 (512, /8), relu5_3 (512, /16)   lpips.py:126-163
+ *   per tap k     f / (sqrt(sum_c f^2) + 1e-10) for both images, (a - b)^2, 1x1 conv C -> 1 without bias (linK),
+ *                 spatial mean                                                                      lpips.py:82-95,166-172
+ *   lpips[n]      = sum over the 5 taps of the means (the reference's [N,1,1,1])
+ * The host drives it as: vt_lpips_prep -> 13 x vt_conv_act (a VGG slice at a time, the input frames and the reconstruction frames
+ * of all pairs in one launch) -> vt_lpips_tap after each slice (its pooled output feeds the next slice) -> vt_lpips_finish.
+ * Deterministic (no floating-point atomics; a fixed partition of the pixels per shape, fixed-order sums), no allocation, no host
+ * synchronisation: graph-capture safe.  Arithmetic of the convolutions: dtype (VT_F32 / VT_BF16 / VT_F16); the head runs in fp32.
+ *
+ * vt_conv_act: vt_conv (same descriptor, same contract) followed by an activation of the fp32 result before the rounding to
+ *   out_dtype; act = VT_ACT_RELU (torch.nn.ReLU after each VGG16 conv, lpips.py:130 via torchvision features).  Supported: dtype
+ *   VT_F32 / VT_BF16 / VT_F16 with out_dtype == dtype, NDHWC output, no residual, no LayerNorm, nbatch 1, no interleave; Cout > 64
+ *   needs Cin a multiple of 16 bytes' worth of K step (32 fp32 / 64 16-bit values).  VGG's first layer: Cin 3 stored as 8.
+ * vt_lpips_prep: x, y fp32 NCTHW [B][3][T][H][W] (T = 1: NCHW) -> out [2N][H][W][8] in dtype, N = B*T, frame n = b*T + t: frames
+ *   0..N-1 from x, N..2N-1 from y, channels 3..7 zero.  Per value, in fp32 and in the reference's statement order:
+ *     flags & VT_LPIPS_CLAMP_Y    y only: clamp(v, -1, 1)                    (output.clamp(-1, 1), inference_evaluate.py:175)
+ *     flags & VT_LPIPS_ROUNDTRIP  u = (v + 1) / 2; v = u * 2 - 1             ((x+1)/2 then inp*2-1, :176,186)
+ *     flags & VT_LPIPS_UNIT       v = v * 2 - 1                              ([0,1] images, the compute_psnr convention)
+ *     (v - shift[c]) / scale[c]                                             (a true division; shift, scale: fp32 [3] on the device)
+ * vt_lpips_tap: feat = relu_k [2N][H][W][C] (dtype, C in 64 / 128 / 256 / 512) of tap k = `tap` (0..4), lin_w fp32 [C]: writes the
+ *   pixel sums of sum_c lin_w[c] (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2 (a = frame n, b = frame n + N) into the
+ *   workspace, and, if pooled != NULL, pooled [2N][H/2][W/2][C] = MaxPool2d(2, 2) of feat (bit-exact; odd sizes floor).
+ * vt_lpips_finish: lpips[n] (fp32 [N]) = sum over taps of the means; tap_means (fp32 [5][N]) or NULL.  H, W: the input size.
+ * work: vt_lpips_work_bytes(N, H, W) bytes (16-byte aligned), shared by the taps and the finish of one LPIPS pass.
+ * Arguments are checked before any device work: VT_ERR_ARG for a dtype other than F32 / BF16 / F16, C outside 64 / 128 / 256 / 512,
+ * null tensors, a workspace below vt_lpips_work_bytes, or an input H or W below 16 (relu5_3 would be empty).
+ * ---------------------------------------------------------------------------------------- */
+#define VT_ACT_RELU 1
+#define VT_LPIPS_CLAMP_Y 1
+#define VT_LPIPS_ROUNDTRIP 2
+#define VT_LPIPS_UNIT 4
+int vt_conv_act(const vt_conv_desc* d, int32_t act, vt_stream stream);
+int64_t vt_lpips_work_bytes(int32_t N, int32_t H, int32_t W);     /* 0 for invalid sizes */
+int vt_lpips_prep(const float* x, const float* y, void* out, const float* shift, const float* scale, int32_t dtype, int32_t B,
+                  int32_t T, int32_t H, int32_t W, int32_t flags, vt_stream stream);
+int vt_lpips_tap(const void* feat, void* pooled, const float* lin_w, void* work, int64_t work_bytes, int32_t dtype, int32_t N,
+                 int32_t H, int32_t W, int32_t C, int32_t tap, vt_stream stream);
+int vt_lpips_finish(const void* work, int64_t work_bytes, float* lpips, float* tap_means, int32_t N, int32_t H, int32_t W,
+                    vt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 
 Layout: `csrc/` HIP kernels + C-ABI (include/vidtok_amd.h), `lib.py` ctypes binding, `ops.py`
 tensor-facing operator wrappers, `modules.py` / `regularizers.py` / `engine.py` the host-side mirror
-of the reference's module API, `config.py` the YAML `target:` plug-in loader.
+of the reference's module API, `config.py` the YAML `target:` plug-in loader, `metrics.py` / `lpips.py`
+the eval loop's PSNR / SSIM / LPIPS.
 """
 from .config import instantiate_from_config, load_config, load_model_from_config  # noqa: F401
 

@@ -310,3 +310,17 @@ extern "C" int vt_conv(const vt_conv_desc* d, vt_stream stream_) {
                           d->ln_eps, d->ln_mode == 2 ? 1 : 0, stream_);
 }
 
+// vt_conv with a ReLU epilogue (VGG16's conv + ReLU pairs, LPIPS): the same descriptor checks, then the ACT = VT_ACT_RELU instantiations of
+// conv_igemm_act.hip -- never the weight-stationary, conv_in8, narrow or split-K kernels, whose epilogues have no activation
+extern "C" int vt_conv_act(const vt_conv_desc* d, int32_t act, vt_stream stream_) {
+  VT_CHECK_ARG(act == VT_ACT_RELU, "vt_conv_act: act %d (VT_ACT_RELU = %d is the one activation)", act, VT_ACT_RELU);
+  ConvArgs a;
+  bool ln_fused = false, use_ws = false;
+  int nbatch = 1;
+  const int rc = conv_prepare(d, a, ln_fused, nbatch, use_ws);
+  if (rc != VT_OK) return rc;
+  VT_CHECK_ARG(d->dtype != VT_BF16X3 && d->out_dtype == d->dtype, "vt_conv_act: fp32, bf16 or fp16 arithmetic with results in the same type");
+  VT_CHECK_ARG(d->out_layout == VT_NDHWC && d->res_mode == VT_RES_NONE && d->ln_mode == 0 && nbatch == 1 && a.yt_mul == 1 && a.ys_mul == 1,
+               "vt_conv_act: NDHWC output without residual, LayerNorm, batching or interleave");
+  return vt_igemm_dispatch_relu(&a, d->dtype, stream_);
+}

@@ -1,0 +1,38 @@
+// Implicit-GEMM convolution kernel (conv_igemm_kernel.h) with a ReLU in the epilogue: the instantiations behind vt_conv_act
+// (conv_igemm.hip validates the descriptor).  Only the tiles the VGG16 feature stack of LPIPS selects are instantiated, in fp32, bf16
+// and fp16 arithmetic with results in the same type:
+//   Cout <= 64          the 256 x 64 tile (4 waves), the tap-walk form or -- Cin = 8, the 3-channel image stored as 8 -- the general one
+//   Cout % 256 == 0     the 8-wave 256 x 256 tile; in a 16-bit type with the LDS-transposed epilogue where it applies (full tiles)
+//   otherwise           the 128 x 128 tile (4 waves), two workgroups per CU
+// The K loops are the ones vt_conv runs; ACT = VT_ACT_RELU changes the epilogues only (max(v, 0) on the fp32 result, then the rounding).
+#include "conv_igemm_kernel.h"
+
+namespace {
+
+template <typename MT>
+int dispatch_relu(const ConvArgs& a, hipStream_t stream) {
+  constexpr int BK = kRowBytes / (int)sizeof(MT);
+  constexpr int R = VT_ACT_RELU;
+  if (a.Cout <= 64) {
+    if (a.Cin % BK == 0) return launch_variant<MT, MT, 4, 1, 2, 2, true, 0, 2, kRowBytes, R>(a, 1, stream);
+    return launch_variant<MT, MT, 4, 1, 2, 2, false, 0, 2, kRowBytes, R>(a, 1, stream);
+  }
+  VT_CHECK_ARG(a.Cin % BK == 0, "vt_conv_act: Cout=%d needs Cin a multiple of %d (got %d)", a.Cout, BK, a.Cin);
+  if (a.Cout % 256 == 0 && (a.ldy & 3) == 0) {
+    if constexpr (is_h16<MT>::value) {
+      if (lds256_plain_eligible(a, 1, true)) return launch_variant<MT, MT, 4, 2, 2, 4, true, 1, 2, kRowBytes, R>(a, 1, stream);
+    }
+    return launch_variant<MT, MT, 4, 2, 2, 4, true, 0, 2, kRowBytes, R>(a, 1, stream);
+  }
+  return launch_variant<MT, MT, 2, 2, 2, 2, true, 0, 2, kRowBytes, R>(a, 1, stream);
+}
+
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int vt_igemm_dispatch_relu(const void* args, int dtype, void* stream) {
+  const ConvArgs& a = *reinterpret_cast<const ConvArgs*>(args);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (dtype == VT_F32) return dispatch_relu<float>(a, s);
+  if (dtype == VT_F16) return dispatch_relu<f16_t>(a, s);
+  return dispatch_relu<bf16_t>(a, s);
+}

@@ -43,6 +43,10 @@
 
 namespace {
 
+// ReLU of the ACT = VT_ACT_RELU epilogues (vt_conv_act): a select, so that -0 and negative results both become +0 (max-pooling the
+// features afterwards is then bit-equal to torch's max_pool2d of them)
+__device__ __forceinline__ float act_relu(float v) { return v > 0.0f ? v : 0.0f; }
+
 // Epilogue shared by both staging variants: + bias, + residual / alpha-mix, dtype conversion, NDHWC
 // vector store (lane = one pixel, 4 consecutive channels per accumulator quad) or NCTHW fp32 store.
 // Two straight-line paths chosen by ONE uniform branch: the fast path (full channel tile, NDHWC,
@@ -50,7 +54,7 @@ namespace {
 // back to back, then the arithmetic, then vector stores -- one memory latency per tile; the general
 // path (ragged channel tails, NCTHW, narrow outputs) does the same per 32-pixel row group with
 // clamped scalar loads.  (The first version branched and waited per element: ~26 us per tile.)
-template <typename TOut, int TM, int TN, bool GENERAL = true>
+template <typename TOut, int TM, int TN, bool GENERAL = true, int ACT = 0>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[TN][TM], int m_blk, int n_blk, int bn_tile,
                                               int wm, int wn, int lane, long long z) {
   TOut* __restrict__ yg = reinterpret_cast<TOut*>(p.y) + z * p.ys_z;
@@ -132,6 +136,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[T
               v[e] = acc[a0 + a][b][4 * g + e] + bq[a][g][e];
               if (p.res_mode == VT_RES_ADD) v[e] = rq[a][b][g].get(e) + v[e];
               if (p.res_mode == VT_RES_MIX) v[e] = alpha * rq[a][b][g].get(e) + (1.0f - alpha) * v[e];
+              if constexpr (ACT == VT_ACT_RELU) v[e] = act_relu(v[e]);
             }
             if (store_ok[b]) store_quad<TOut>(yg + mrow[b] * p.ldy + nq + 32 * (a0 + a) + 8 * g, v);
           }
@@ -162,6 +167,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[T
           float v = acc[a][b][4 * g + e] + bv[g][e];
           if (p.res_mode == VT_RES_ADD) v = rv[g][e] + v;
           if (p.res_mode == VT_RES_MIX) v = alpha * rv[g][e] + (1.0f - alpha) * v;
+          if constexpr (ACT == VT_ACT_RELU) v = act_relu(v);
           if (store_ok[b] && n < p.Cout) {
             if (p.out_layout == VT_NCTHW)
               yg[ybase[b] + (long long)n * (p.To - p.t_trim) * HWo] = from_f32<TOut>(v);
@@ -188,7 +194,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[T
 // NA x NB: the wave's accumulators cover channels [c_base, c_base + 32 NA) x pixel rows [prow_base, prow_base + 32 NB) of the tile:
 // 2 x 2 at (64 wn, 64 wm) for the implicit-GEMM kernel's wave grid.  conv_in8_kernel's 1 x 4 grid has its own two-pass copy of this
 // row phase, conv_epilogue_in8, on a 64-row buffer.)
-template <typename TOut, bool ALLOW_RES = true, int NA = 2, int NB = 2>
+template <typename TOut, bool ALLOW_RES = true, int NA = 2, int NB = 2, int ACT = 0>
 __device__ __forceinline__ void conv_epilogue_lds128_at(const ConvArgs& p, f32x16 (&acc)[NA][NB], int m_blk, int n_blk, int c_base,
                                                         int prow_base, int lane, int tid, char* smem, long long z) {
   TOut* __restrict__ yg = reinterpret_cast<TOut*>(p.y) + z * p.ys_z;
@@ -268,6 +274,7 @@ __device__ __forceinline__ void conv_epilogue_lds128_at(const ConvArgs& p, f32x1
       v[e] = e < 4 ? t0[e] : t1[e - 4];
       if (ALLOW_RES && p.res_mode == VT_RES_ADD) v[e] = rq[it].get(e) + v[e];
       if (ALLOW_RES && p.res_mode == VT_RES_MIX) v[e] = alpha * rq[it].get(e) + (1.0f - alpha) * v[e];
+      if constexpr (ACT == VT_ACT_RELU) v[e] = act_relu(v[e]);
     }
     const long long orow = out_row(p, m_blk + row);
     if (!p.ln_mode || p.ln_keep_y) Oct<TOut>::store(yg + orow * p.ldy + n_blk + 8 * oct_j, v, p.nt_store != 0);
@@ -299,10 +306,10 @@ __device__ __forceinline__ void conv_epilogue_lds128_at(const ConvArgs& p, f32x1
   }
 }
 
-template <typename TOut>
+template <typename TOut, int ACT = 0>
 __device__ __forceinline__ void conv_epilogue_lds128(const ConvArgs& p, f32x16 (&acc)[2][2], int m_blk, int n_blk, int wm,
                                                      int wn, int lane, int tid, char* smem, long long z) {
-  conv_epilogue_lds128_at<TOut, true, 2, 2>(p, acc, m_blk, n_blk, wn * 64, wm * 64, lane, tid, smem, z);
+  conv_epilogue_lds128_at<TOut, true, 2, 2, ACT>(p, acc, m_blk, n_blk, wn * 64, wm * 64, lane, tid, smem, z);
 }
 
 // LayerNorm-fusing / row-coalescing epilogue of the 8-wave 256 x 256 tile (Cout % 256 == 0; with a LayerNorm: Cout = 256, so the two
@@ -319,7 +326,7 @@ __device__ __forceinline__ void conv_epilogue_lds128(const ConvArgs& p, f32x16 (
 // LDS layout: T[128 rows][64 chunks of 4 floats], chunk index XOR (row & 63); row w*32 + l of half b = tile pixel
 // w*64 + b*32 + l.  A lane's two chunks (2j, 2j+1) make its ds_read_b128 pair 2-way bank-conflicted (16 lanes of a service
 // group hit 8 bank quads); the LDS is idle here, the global accesses are what counts.
-template <typename TOut>
+template <typename TOut, int ACT = 0>
 __device__ __forceinline__ void conv_epilogue_lds256(const ConvArgs& p, f32x16 (&acc)[4][2], int m_blk, int n_blk, int wm, int wn, int lane,
                                                      int tid, char* smem, long long z) {
 #pragma clang fp contract(off)
@@ -392,6 +399,10 @@ __device__ __forceinline__ void conv_epilogue_lds256(const ConvArgs& p, f32x16 (
       } else if (p.res_mode == VT_RES_MIX) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = f32x2{rq[it].get(2 * q), rq[it].get(2 * q + 1)} * alpha + v[q] * (1.0f - alpha);
+      }
+      if constexpr (ACT == VT_ACT_RELU) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = f32x2{act_relu(v[q][0]), act_relu(v[q][1])};
       }
       if (p.ln_keep_y || !has_ln) {
         const float yv[8] = {v[0][0], v[0][1], v[1][0], v[1][1], v[2][0], v[2][1], v[3][0], v[3][1]};
@@ -477,7 +488,9 @@ __device__ __forceinline__ void conv_epilogue_lds256(const ConvArgs& p, f32x16 (
 //        register allocation (round 1)
 // SCHED  K-step schedule of the 8-wave tile on descriptors: 0 plain loop (also every 4-wave tile and the pointer form), 1 software-
 //        pipelined single body (fp32 operands), 2 two-group ping-pong (16-bit operands), 5 two groups for the split-bf16 arithmetic
-template <typename MT, typename TOut, int WAVES_M, int WAVES_N, int TM, int TN, bool FAST, int ROWB, int STAGES, bool BUF, int LN256 = 0, bool PROF = false, int SCHED = 0>
+// ACT    activation of the epilogue, applied to the fp32 result before the rounding to TOut: 0 none (every vt_conv instantiation),
+//        VT_ACT_RELU (vt_conv_act, conv_igemm_act.hip) -- a compile-time variant, so the K loop and the epilogues of ACT = 0 are untouched
+template <typename MT, typename TOut, int WAVES_M, int WAVES_N, int TM, int TN, bool FAST, int ROWB, int STAGES, bool BUF, int LN256 = 0, bool PROF = false, int SCHED = 0, int ACT = 0>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_igemm_glds_kernel(const ConvArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)   // device pass only: the host pass needs just the launch stub (buffer-descriptor types are device-only)
   constexpr int THREADS = 64 * WAVES_M * WAVES_N;   // 4 waves (128x128, 256x32/64 tiles) or 8 waves (256x256)
@@ -1297,22 +1310,22 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_igemm_glds_ker
     static_assert(WAVES_M == 4 && WAVES_N == 2 && TM == 2 && TN == 4 && std::is_same<typename storage_of<MT>::type, TOut>::value, "LN256: the 8-wave 256 x 256 tile");
     static_assert(STAGES * STAGE_BYTES >= 128 * 256 * 4, "LN256: the transposition tile must fit the ring");
     if constexpr (!BUF) wait_vmcnt<0>();
-    conv_epilogue_lds256<TOut>(p, acc, m_blk, n_blk, wm, wn, lane, tid, smem, z);
+    conv_epilogue_lds256<TOut, ACT>(p, acc, m_blk, n_blk, wm, wn, lane, tid, smem, z);
     return;
   }
   if constexpr (WAVES_M == 2 && WAVES_N == 2 && TM == 2 && TN == 2 && STAGES * STAGE_BYTES >= 128 * 128 * 4) {
     // full tile, NDHWC, 4-aligned strides (uniform): the coalesced epilogue through the LDS
     if (p.lds_epi && m_blk + BM <= p.M && n_blk + BN <= p.Cout) {
       if constexpr (!BUF) wait_vmcnt<0>();
-      conv_epilogue_lds128<TOut>(p, acc, m_blk, n_blk, wm, wn, lane, tid, smem, z);
+      conv_epilogue_lds128<TOut, ACT>(p, acc, m_blk, n_blk, wm, wn, lane, tid, smem, z);
       return;
     }
   }
-  conv_epilogue<TOut, TM, TN, (TM * TN < 8)>(p, acc, m_blk, n_blk, BN, wm, wn, lane, z);
+  conv_epilogue<TOut, TM, TN, (TM * TN < 8), ACT>(p, acc, m_blk, n_blk, BN, wm, wn, lane, z);
 #endif
 }
 
-template <typename MT, typename TOut, int WAVES_M, int WAVES_N, int TM, int TN, bool FAST, int LN256 = 0, int STAGES = 2, int ROWB = kRowBytes>
+template <typename MT, typename TOut, int WAVES_M, int WAVES_N, int TM, int TN, bool FAST, int LN256 = 0, int STAGES = 2, int ROWB = kRowBytes, int ACT = 0>
 int launch_variant(const ConvArgs& a_in, int nbatch, hipStream_t stream) {
   constexpr int BM = WAVES_M * TM * 32;
   constexpr int BN = WAVES_N * TN * 32;
@@ -1364,13 +1377,13 @@ int launch_variant(const ConvArgs& a_in, int nbatch, hipStream_t stream) {
     a.x_bytes = (unsigned)xb;
     a.w_bytes = (unsigned)wb;
     a.c_bytes = (unsigned)cb;
-    kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, true, LN256, false, SCHED_BUF>);
+    kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, true, LN256, false, SCHED_BUF, ACT>);
   } else {
-    kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, false, LN256, false, 0>);
+    kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, false, LN256, false, 0, ACT>);
   }
   int lds_bytes = LDS;
   if (a.prof != nullptr) {   // vt_conv_profile: the scheduled 8-wave instantiations of bf16 and split-bf16 (no LayerNorm) carry the stamps
-    if constexpr (EIGHT && FAST && LN256 == 0 && (SCHED_BUF == 2 || SCHED_BUF == 5) && !std::is_same<MT, f16_t>::value &&
+    if constexpr (EIGHT && FAST && LN256 == 0 && ACT == 0 && (SCHED_BUF == 2 || SCHED_BUF == 5) && !std::is_same<MT, f16_t>::value &&
                   std::is_same<typename storage_of<MT>::type, TOut>::value) {
       VT_CHECK_ARG(buf, "vt_conv_profile: descriptor gather only");
       kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, true, 0, true, SCHED_BUF>);

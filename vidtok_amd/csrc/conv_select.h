@@ -128,6 +128,7 @@ extern "C" int vt_igemm_dispatch_f32(const void* args, int nbatch, void* stream)
 extern "C" int vt_igemm_dispatch_x3(const void* args, int nbatch, void* stream);                      // split-bf16 arithmetic, fp32 storage
 extern "C" int vt_igemm_dispatch_bf16(const void* args, int nbatch, int out_f32, void* stream);       // bf16 -> bf16 | fp32
 extern "C" int vt_igemm_dispatch_f16(const void* args, int nbatch, int out_f32, void* stream);        // fp16 -> fp16 | fp32
+extern "C" int vt_igemm_dispatch_relu(const void* args, int dtype, void* stream);                   // conv_igemm_act.hip: + ReLU, in the arithmetic type
 extern "C" int vt_ws2_launch(const void* conv_args, int dtype, void* stream);                         // conv_ws2.hip
 extern "C" int vt_conv_in8_launch(const void* conv_args, int dtype, void* stream);                    // conv_in8.hip
 extern "C" int vt_conv_narrow_launch(const void* conv_args, void* stream, int mode);                  // conv_narrow.hip (mode: 0 bf16, 1 fp16, 2 split-bf16: fp32 x, two passes)

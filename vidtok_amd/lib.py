@@ -20,6 +20,8 @@ VT_TPAD_ZERO, VT_TPAD_REPLICATE, VT_TPAD_CACHE, VT_TPAD_ZERO_BACK = 0, 1, 2, 3
 VT_GN_FRAME, VT_GN_PIXEL, VT_GN_CLIP = 0, 1, 2
 VT_RES_NONE, VT_RES_ADD, VT_RES_MIX = 0, 1, 2
 VT_NDHWC, VT_NCTHW = 0, 1
+VT_ACT_RELU = 1
+VT_LPIPS_CLAMP_Y, VT_LPIPS_ROUNDTRIP, VT_LPIPS_UNIT = 1, 2, 4
 
 
 class VtError(RuntimeError):
@@ -155,6 +157,11 @@ SIGNATURES = {
     "vt_eval_work_floats": (_I64, [_I32, _I32]),
     "vt_eval_psnr_ssim": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "vt_gather_frames": (C.c_int, [_P, _P, _I32, _I32, _I64, _I64, _I64, C.POINTER(_I32), _I32, _P]),
+    "vt_conv_act": (C.c_int, [C.POINTER(ConvDesc), _I32, _P]),
+    "vt_lpips_work_bytes": (_I64, [_I32, _I32, _I32]),
+    "vt_lpips_prep": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "vt_lpips_tap": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "vt_lpips_finish": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _I32, _P]),
 }
 
 _lib = None

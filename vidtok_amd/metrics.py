@@ -36,3 +36,20 @@ def evaluate_clip(model, x):
         xrec = xrec[:, :, -x.shape[2]:] if xrec.shape[2] != x.shape[2] else xrec
         psnr, ssim = _frames(x, xrec, True)
     return xrec, psnr, ssim
+
+
+def compute_lpips(x, y, lpips):
+    """mean LPIPS of [0,1] images x, y (4-D NCHW or 5-D NCTHW) with a vidtok_amd.lpips.LPIPS: the reference calls LPIPS on x*2-1, y*2-1"""
+    from . import lib as L
+
+    x, y = _as5d(x), _as5d(y)
+    assert x.shape == y.shape
+    return lpips.values(x, y, L.VT_LPIPS_UNIT).mean()
+
+
+def evaluate_clip_lpips(model, x, lpips):
+    """evaluate_clip plus the eval loop's third metric: (reconstruction, psnr [B,T], ssim [B,T], lpips [B,T]); LPIPS of the clamped,
+    (.+1)/2-mapped frames exactly as scripts/inference_evaluate.py:175-186 computes it (per-frame values; the reference's split means are
+    means of these)"""
+    xrec, psnr, ssim = evaluate_clip(model, x)
+    return xrec, psnr, ssim, lpips.frames(x, xrec, eval_loop=True)

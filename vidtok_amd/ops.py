@@ -755,3 +755,71 @@ def ncthw_copy_frames(src, dst, ts0, td0, n, clamp=False):
     L.check(lib.vt_ncthw_copy_frames(_ptr(src), _ptr(dst), src.shape[0] * src.shape[1], src.shape[2], dst.shape[2], ts0, td0, n,
                                      src.shape[3] * src.shape[4], int(bool(clamp)), _stream()), "vt_ncthw_copy_frames")
     return dst
+
+
+# ---- LPIPS (include/vidtok_amd.h, vt_conv_act / vt_lpips_*) -----------------------------------------------------------
+def conv_act(x, w, bias, geom: ConvGeom, *, cout: int, act=L.VT_ACT_RELU):
+    """y = act(conv(x) + bias) in x's dtype (vt_conv_act): x [B,Ti,Hi,Wi,Cin], w packed [cout, ldw], bias fp32 [cout] or None;
+    y [B,To,Ho,Wo,cout]"""
+    lib = L.load()
+    _chk(x, "conv_act.x"); _chk(w, "conv_act.w")
+    assert w.dtype == x.dtype and x.dtype in _DT, (w.dtype, x.dtype)
+    B, Ti, Hi, Wi, Cin = x.shape
+    To, Ho, Wo = geom.out_dims(Ti, Hi, Wi)
+    y = torch.empty((B, To, Ho, Wo, cout), dtype=x.dtype, device=x.device)
+    d = L.ConvDesc()
+    d.x, d.w, d.y = x.data_ptr(), w.data_ptr(), y.data_ptr()
+    if bias is not None:
+        _chk(bias, "conv_act.bias")
+        assert bias.dtype == torch.float32 and bias.numel() >= cout
+        d.bias = bias.data_ptr()
+    d.B, d.Ti, d.Hi, d.Wi, d.Cin = B, Ti, Hi, Wi, Cin
+    d.To, d.Ho, d.Wo, d.Cout = To, Ho, Wo, cout
+    d.ldw, d.ldy = w.shape[1], cout
+    d.KT, d.KH, d.KW = geom.kt, geom.kh, geom.kw
+    d.st, d.sh, d.sw = geom.st, geom.sh, geom.sw
+    d.pt, d.ph, d.pw = geom.pt, geom.ph, geom.pw
+    d.dtype = d.out_dtype = _DT[x.dtype]
+    d.nbatch = 1
+    L.check(lib.vt_conv_act(C.byref(d), int(act), _stream()), "vt_conv_act")
+    return y
+
+
+def lpips_work_bytes(n: int, h: int, w: int) -> int:
+    return int(L.load().vt_lpips_work_bytes(n, h, w))
+
+
+def lpips_prep(x, y, shift, scale, dtype, flags=0):
+    """vt_lpips_prep: x, y fp32 NCTHW [B,3,T,H,W] (or NCHW [N,3,H,W]) -> the scaled NHWC stack [2N, H, W, 8] in `dtype`
+    (x's frames first); flags: L.VT_LPIPS_CLAMP_Y | L.VT_LPIPS_ROUNDTRIP | L.VT_LPIPS_UNIT"""
+    lib = L.load()
+    _chk(x, "lpips_prep.x"); _chk(y, "lpips_prep.y"); _chk(shift, "lpips_prep.shift"); _chk(scale, "lpips_prep.scale")
+    assert x.dtype == torch.float32 and y.dtype == torch.float32 and x.shape == y.shape and x.dim() in (4, 5) and x.shape[1] == 3
+    B, T, H, W = (x.shape[0], 1, x.shape[2], x.shape[3]) if x.dim() == 4 else (x.shape[0], x.shape[2], x.shape[3], x.shape[4])
+    out = torch.empty((2 * B * T, H, W, 8), dtype=dtype, device=x.device)
+    L.check(lib.vt_lpips_prep(_ptr(x), _ptr(y), _ptr(out), _ptr(shift), _ptr(scale), _DT[dtype], B, T, H, W, int(flags), _stream()),
+            "vt_lpips_prep")
+    return out
+
+
+def lpips_tap(feat, lin_w, work, tap: int, pool: bool = True):
+    """vt_lpips_tap over relu_k feat [2N, H, W, C]: the head's pixel sums go into `work`; returns the 2 x 2 max-pooled
+    [2N, H/2, W/2, C] (pool=True) or None"""
+    lib = L.load()
+    _chk(feat, "lpips_tap.feat"); _chk(lin_w, "lpips_tap.lin_w"); _chk(work, "lpips_tap.work")
+    assert feat.dim() == 4 and feat.shape[0] % 2 == 0 and lin_w.dtype == torch.float32 and lin_w.numel() == feat.shape[3]
+    n2, H, W, Cc = feat.shape
+    pooled = torch.empty((n2, H // 2, W // 2, Cc), dtype=feat.dtype, device=feat.device) if pool else None
+    L.check(lib.vt_lpips_tap(_ptr(feat), _ptr(pooled), _ptr(lin_w), _ptr(work), work.numel() * work.element_size(), _DT[feat.dtype],
+                             n2 // 2, H, W, Cc, int(tap), _stream()), "vt_lpips_tap")
+    return pooled
+
+
+def lpips_finish(work, n: int, h: int, w: int, tap_means: bool = False):
+    """vt_lpips_finish -> lpips [N] fp32 (and the per-tap means [5, N] with tap_means=True)"""
+    lib = L.load()
+    _chk(work, "lpips_finish.work")
+    out = torch.empty((n,), dtype=torch.float32, device=work.device)
+    taps = torch.empty((5, n), dtype=torch.float32, device=work.device) if tap_means else None
+    L.check(lib.vt_lpips_finish(_ptr(work), work.numel() * work.element_size(), _ptr(out), _ptr(taps), n, h, w, _stream()), "vt_lpips_finish")
+    return (out, taps) if tap_means else out

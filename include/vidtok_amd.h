@@ -518,6 +518,41 @@ int vt_tile_decode(vt_model* h, const float* z, int32_t B, int32_t Tz, int32_t H
                    float* x_out, void* workspace, int64_t workspace_bytes, vt_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sessions of the v1.1 models (version 1): the temporal tiling above, fed as the frames arrive -- a live feed, a camera, the
+ * tokens of an autoregressive model -- instead of from one whole clip.  Same chunk schedule ([0,1), [1,1+c), [1+c,1+2c) ...),
+ * same kernels: the concatenated outputs of push* + finish equal vt_tile_encode / vt_tile_decode byte for byte, however the
+ * input is split into pushes.  A session owns its causal state (one buffer per module cache) and the frames of its incomplete
+ * chunk, both sized at create by a dry walk, so a push runs no hipMalloc and no device synchronisation, and device memory is
+ * bounded by the chunk, not by the length of the video.  Several sessions may be open on one handle: each push swaps the
+ * session's state in for its duration (one call at a time per handle, as for every other call).
+ *   vt_session_create(h, kind, B, H, W, t_chunk, use_overlap, &s)
+ *       kind VT_SESSION_ENCODE: frames [B][in_channels][n][H][W] in, pre-regularizer moments [B][C'][n'][H'][W'] out (the caller
+ *         runs vt_regularize_* on each emitted slice, as after vt_tile_encode); t_chunk = t_chunk_enc, a multiple of the
+ *         temporal factor f.  Chunk 0 is the first frame alone: its latent comes back from the first push.
+ *       kind VT_SESSION_DECODE: latents [B][z_channels][n][H'][W'] in (H, W = H', W'), frames [B][out_ch][n][H'*s][W'*s] out;
+ *         t_chunk = t_chunk_dec.  Without overlap a chunk is decoded when it is complete; with use_overlap, once the latent
+ *         after it has arrived (one latent frame of latency) or at finish.
+ *   vt_session_workspace_bytes(s)          workspace of every push / finish of the session (-1: bad session)
+ *   vt_session_push(s, in, n, out, out_cap_frames, &n_out, ws, ws_bytes, stream)   n >= 1 frames; writes the n_out frames of
+ *                                          every chunk the push completed to out[:, :, 0:n_out] (out has out_cap_frames frames;
+ *                                          at most (n + t_chunk) / f + 1 latent frames for an encode, (n + t_chunk + 1) * f
+ *                                          frames for a decode; a push that would not fit is refused before anything runs)
+ *   vt_session_finish(s, out, out_cap_frames, &n_out, ws, ws_bytes, stream)   runs the incomplete last chunk, if any; the
+ *                                          session takes no frames afterwards
+ *   vt_session_destroy(s)                  frees the session's buffers (synchronises the device: work may still be queued on them)
+ * ---------------------------------------------------------------------------------------- */
+#define VT_SESSION_ENCODE 0
+#define VT_SESSION_DECODE 1
+typedef struct vt_session vt_session;
+int vt_session_create(vt_model* h, int32_t kind, int32_t B, int32_t H, int32_t W, int32_t t_chunk, int32_t use_overlap, vt_session** out);
+int64_t vt_session_workspace_bytes(const vt_session* s);
+int vt_session_push(vt_session* s, const float* in, int32_t n, float* out, int32_t out_cap_frames, int32_t* n_out, void* workspace,
+                    int64_t workspace_bytes, vt_stream stream);
+int vt_session_finish(vt_session* s, float* out, int32_t out_cap_frames, int32_t* n_out, void* workspace, int64_t workspace_bytes,
+                      vt_stream stream);
+int vt_session_destroy(vt_session* s);
+
+/* ------------------------------------------------------------------------------------------
  * Video front / back end around model(x): the device halves of scripts/inference_reconstruct.py (the codec --
  * decord / torchvision.io.write_video -- stays with the caller).  B = 1 like the reference's DataLoader.
  * vt_frames_u8_to_ncthw: decoded frames uint8 [T][H0][W0][3] -> x fp32 [3][Tdst][H][W], frames t_off .. t_off+T:
@@ -546,6 +581,17 @@ int vt_ncthw_copy_frames(const float* src, float* dst, int32_t C, int32_t Ts, in
 int vt_gather_frames(const void* src, void* dst, int32_t esize, int32_t B, int64_t frame_elems,
                      int64_t src_bstride, int64_t dst_bstride, const int32_t* idx_host, int32_t n,
                      vt_stream stream);
+
+/* many small device-to-device copies in one launch: entry i of `table` (a DEVICE array of n entries) copies bytes_i bytes from
+ * src_i to dst_i (ranges must not overlap).  16-byte vector accesses where both ends are 16-byte aligned, narrower otherwise; any
+ * size.  The table is read on the device, so the launch may be captured into a graph.  `max_bytes` (the largest entry, or any
+ * estimate) only sizes the grid.  A session switch of a v1.1 model (its dozens of chunk caches in / out) is two such launches. */
+typedef struct vt_copy_segment {
+  const void* src;
+  void* dst;
+  int64_t bytes;
+} vt_copy_segment;
+int vt_copy_segments(const vt_copy_segment* table, int32_t n, int64_t max_bytes, vt_stream stream);
 
 /* nn.Linear along the channel axis of an NCTHW fp32 tensor viewed as [B][Cin][S] -> [B][Cout][S]:
  * FSQRegularizer.project_in / project_out when dim != len(levels) (vidtok/modules/regularizers.py:137-139,225,255).

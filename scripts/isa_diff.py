@@ -76,6 +76,9 @@ def main(argv):
     for n in new:
         k = n[: -len(ACT0_SUFFIX[0])] + ACT0_SUFFIX[1] if "conv_igemm_glds_kernel" in n and n.endswith(ACT0_SUFFIX[0]) else n
         new_by_old_name[k] = n
+    for n in new:                  # both builds after the ACT argument: a kernel pairs with its own name first
+        if n in old:
+            new_by_old_name[n] = n
     same, changed, missing, renamed = 0, [], [], 0
     for name, ins in sorted(old.items()):
         if name not in new_by_old_name:

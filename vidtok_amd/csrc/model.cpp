@@ -139,6 +139,7 @@ struct CState {
   size_t cap = 0;
   int frames = 0;                  // frames held (0 = nothing cached yet)
   int offset = 0;
+  size_t need = 0;                 // the most a dry walk asked of the buffer (sizes a session's state at vt_session_create)
 };
 
 struct Model {
@@ -149,7 +150,10 @@ struct Model {
   std::vector<std::unique_ptr<DevBuf>> retired;   // outgrown cache buffers: work queued on them may still run; freed at reset / destroy
   // the cache buffer of `st` with room for `bytes` (grown by a synchronous hipMalloc the first time a chunk kind needs it)
   char* persistent(CState& st, size_t bytes, bool dry) {
-    if (dry) return nullptr;
+    if (dry) {
+      st.need = std::max(st.need, bytes);
+      return nullptr;
+    }
     if (st.cap < bytes) {
       auto b = std::make_unique<DevBuf>();
       if (hipMalloc(&b->p, bytes) != hipSuccess) {
@@ -1718,4 +1722,247 @@ extern "C" int vt_regularize_fsq_aux(vt_model* h, const float* pre, int32_t B, i
     vt_set_error("vt_regularize_fsq_aux: %s", e.what());
     return VT_ERR_ARG;
   }
+}
+
+// ---- sessions: the v1.1 tiling fed as the frames arrive (include/vidtok_amd.h, "Sessions") ----------------------------------------
+// A session is the loop of tile_encode_impl / tile_decode_impl turned inside out: the chunk schedule advances with every push, the
+// frames of the incomplete chunk wait in a buffer of the session's own, and the per-module causal state lives in CStates owned by the
+// session -- swapped into the graph for the length of a push (SessionSwap), so that any number of sessions, and the handle's own
+// vt_tile_* / vt_encode calls, can take turns on one handle.  Swapping moves pointers, not bytes: the C host captures no graphs.
+struct vt_session {
+  vt_model* h = nullptr;
+  int kind = VT_SESSION_ENCODE;
+  int B = 0, H = 0, W = 0, c = 0;  // H, W: of the input (frames of an encode, latents of a decode); c: chunk length in input frames
+  bool overlap = false;            // decode: one look-ahead latent frame per chunk
+  int cin = 0, cout = 0, Ho = 0, Wo = 0, f = 1;
+  std::vector<CState> st;          // the session's causal state, in the order of Graph::states
+  DevBuf pend;                     // frames of the incomplete chunk, fp32 [B][cin][cap][H][W]
+  int cap = 0, npend = 0;
+  int chunks = 0;                  // chunks run so far
+  bool finished = false, broken = false;
+  size_t staging = 0;              // chunk staging at the front of the workspace
+  int64_t ws_bytes = 0;
+  Graph& graph() { return kind == VT_SESSION_ENCODE ? h->enc : h->dec; }
+};
+
+namespace {
+
+struct SessionSwap {               // the session's causal state in the graph for the length of a push; the handle's own back on every exit
+  vt_session* s;
+  std::vector<CState*> g;
+  explicit SessionSwap(vt_session* s_) : s(s_) {
+    s->graph().states(g);
+    swap();
+  }
+  ~SessionSwap() { swap(); }
+  void swap() {
+    for (size_t i = 0; i < g.size(); ++i) {
+      std::swap(g[i]->buf, s->st[i].buf);
+      std::swap(g[i]->cap, s->st[i].cap);
+      std::swap(g[i]->frames, s->st[i].frames);
+    }
+  }
+  SessionSwap(const SessionSwap&) = delete;
+  SessionSwap& operator=(const SessionSwap&) = delete;
+};
+
+// one step of a push: copy `k` input frames from `in_t0` into the pending buffer, or run the pending frames [0, nl) as chunk `idx`
+struct SessionOp {
+  bool run;
+  int in_t0, k;                    // copy
+  int nl, idx, n_out;              // run: input frames, chunk index, output frames kept
+  bool look;
+};
+
+int session_chunk_len(const vt_session* s, int idx) { return idx == 0 ? 1 : s->c; }
+
+// the host side of a push / finish, before anything runs: which frames go where, which chunks complete, how many frames come out
+std::vector<SessionOp> session_plan(const vt_session* s, int n, bool fin, int* npend_after, int* chunks_after, int* frames_out) {
+  std::vector<SessionOp> ops;
+  int np = s->npend, ch = s->chunks, t = 0, outf = 0;
+  const bool dec = s->kind == VT_SESSION_DECODE;
+  auto run = [&](int nl, bool look) {
+    const int n_out = dec ? nl * s->f - (look ? s->f : 0) : ceil_div(nl, s->f);
+    ops.push_back(SessionOp{true, 0, 0, nl, ch, n_out, look});
+    outf += n_out;
+    ++ch;
+  };
+  while (t < n) {
+    const int len = session_chunk_len(s, ch), want = len + (dec && s->overlap ? 1 : 0);
+    const int k = std::min(want - np, n - t);
+    ops.push_back(SessionOp{false, t, k, 0, 0, 0, false});
+    np += k;
+    t += k;
+    if (np == want) {
+      run(want, dec && s->overlap);
+      np = want - len;             // the look-ahead latent stays: it opens the next chunk
+    }
+  }
+  if (fin && np > 0) {
+    run(np, false);
+    np = 0;
+  }
+  *npend_after = np;
+  *chunks_after = ch;
+  *frames_out = outf;
+  return ops;
+}
+
+int session_step(vt_session* s, const float* in, int n, float* out, int out_cap, int* n_out, void* ws, int64_t ws_bytes, hipStream_t stream, bool fin,
+                 const char* what) {
+  M_CHECK(s != nullptr && s->h != nullptr && n_out != nullptr, "%s: null argument", what);
+  M_CHECK(!s->broken, "%s: an earlier call on this session failed half way; its state is undefined (destroy it)", what);
+  M_CHECK(!s->finished, "%s: the session is finished (vt_session_finish ran): it takes no more frames", what);
+  int np, ch, outf;
+  const std::vector<SessionOp> plan = session_plan(s, n, fin, &np, &ch, &outf);
+  M_CHECK(outf == 0 || out != nullptr, "%s: null output", what);
+  M_CHECK(outf <= out_cap, "%s: %d output frames do not fit into out_cap_frames = %d", what, outf, out_cap);
+  M_CHECK(ws_bytes >= s->ws_bytes, "%s: workspace too small (%lld bytes; ask vt_session_workspace_bytes: %lld)", what, (long long)ws_bytes,
+          (long long)s->ws_bytes);
+  Model& m = s->h->m;
+  const int64_t hw = (int64_t)s->H * s->W, hwo = (int64_t)s->Ho * s->Wo;
+  const bool dec = s->kind == VT_SESSION_DECODE;
+  s->broken = true;
+  {
+    bind_workspace(m, ws, ws_bytes, s->staging);
+    const ChunkBufs cb = chunk_bufs(ws, (size_t)s->B * s->cin * s->cap * hw, 0);     // inside the staging vt_session_create sized
+    SessionSwap swap(s);
+    TileScope scope(&m, s->graph(), dec && s->overlap);
+    int npend = s->npend, done = 0;
+    for (const SessionOp& op : plan) {
+      if (!op.run) {
+        M_CALL(vt_ncthw_copy_frames(in, (float*)s->pend.p, s->B * s->cin, n, s->cap, op.in_t0, npend, op.k, hw, 0, stream));
+        npend += op.k;
+        continue;
+      }
+      const float* x = (const float*)s->pend.p;
+      if (op.nl != s->cap) {       // the chunk as a tensor of its own length (the pending buffer is laid out for `cap` frames)
+        M_CALL(vt_ncthw_copy_frames(x, cb.in, s->B * s->cin, s->cap, op.nl, 0, 0, op.nl, hw, 0, stream));
+        x = cb.in;
+      }
+      m.first_chunk = op.idx == 0;
+      const int nres = dec ? op.nl * s->f : ceil_div(op.nl, s->f);
+      if (dec) decode_impl(&m, s->graph(), x, s->B, op.nl, s->H, s->W, cb.out, stream, false);
+      else encode_impl(&m, s->graph(), x, s->B, op.nl, s->H, s->W, cb.out, stream, false);
+      M_CALL(vt_ncthw_copy_frames(cb.out, out, s->B * s->cout, nres, out_cap, 0, done, op.n_out, hwo, 0, stream));
+      done += op.n_out;
+      if (op.look)                 // the look-ahead latent opens the next chunk
+        M_CALL(vt_ncthw_copy_frames((const float*)s->pend.p, (float*)s->pend.p, s->B * s->cin, s->cap, s->cap, op.nl - 1, 0, 1, hw, 0, stream));
+      npend = op.look ? 1 : 0;
+    }
+  }
+  s->npend = np;
+  s->chunks = ch;
+  s->finished = fin;
+  s->broken = false;
+  *n_out = outf;
+  return VT_OK;
+}
+
+}  // namespace
+
+extern "C" int vt_session_create(vt_model* h, int32_t kind, int32_t B, int32_t H, int32_t W, int32_t t_chunk, int32_t use_overlap, vt_session** out) {
+  try {
+    M_CHECK(out != nullptr, "vt_session_create: null argument");
+    *out = nullptr;
+    M_CHECK(h != nullptr, "vt_session_create: null handle");
+    M_CHECK(h->m.v11(), "vt_session_create: sessions exist only for the v1.1 models (version 1): the v1.0 and non-causal models have no chunk protocol");
+    M_CHECK(kind == VT_SESSION_ENCODE || kind == VT_SESSION_DECODE, "vt_session_create: kind must be VT_SESSION_ENCODE or VT_SESSION_DECODE");
+    M_CHECK(B > 0 && H > 0 && W > 0 && t_chunk > 0, "vt_session_create: bad argument");
+    Model& m = h->m;
+    const vt_model_config& cf = m.cfg;
+    const int f = cf.time_downsample_factor;
+    auto s = std::make_unique<vt_session>();
+    s->h = h;
+    s->kind = kind;
+    s->B = B; s->H = H; s->W = W; s->c = t_chunk; s->f = f;
+    s->overlap = kind == VT_SESSION_DECODE && use_overlap != 0;
+    if (kind == VT_SESSION_ENCODE) {
+      M_CHECK(t_chunk % f == 0, "vt_session_create: t_chunk_enc (%d) must be a multiple of the temporal factor %d", t_chunk, f);
+      const int ds = 1 << cf.n_spatial_ds;
+      M_CHECK(H % ds == 0 && W % ds == 0, "vt_session_create: H and W must be multiples of %d", ds);
+      check_loaded(h, "encoder.");
+      s->cin = cf.in_channels;
+      s->cout = cf.double_z ? 2 * cf.z_channels : cf.z_channels;
+      s->Ho = H >> cf.n_spatial_ds; s->Wo = W >> cf.n_spatial_ds;
+      s->cap = t_chunk;
+      s->staging = tile_staging_bytes(cf, B, H, W, t_chunk);
+    } else {
+      check_loaded(h, "decoder.");
+      s->cin = cf.z_channels;
+      s->cout = cf.out_ch;
+      s->Ho = H << cf.n_spatial_us; s->Wo = W << cf.n_spatial_us;
+      s->cap = t_chunk + (s->overlap ? 1 : 0);
+      s->staging = tile_staging_bytes(cf, B, s->Ho, s->Wo, t_chunk * f);
+    }
+    // dry walks over every chunk kind the schedule can meet (each chunk length after the first, with and without the look-ahead
+    // frame): the arenas' peak sizes the workspace, the caches' sizes the session's state
+    std::vector<CState*> gs;
+    s->graph().states(gs);
+    for (CState* g : gs) g->need = 0;
+    size_t peak = 0;
+    {
+      ArenaScope arenas(&m);
+      if (kind == VT_SESSION_ENCODE)
+        for (int n = 1; n <= t_chunk; ++n) tile_encode_impl(&m, h->enc, nullptr, B, 1 + n, H, W, t_chunk, nullptr, nullptr, nullptr, true);
+      else
+        for (int n = 1; n <= t_chunk + 2; ++n) tile_decode_impl(&m, h->dec, nullptr, B, n, H, W, t_chunk, s->overlap, nullptr, nullptr, nullptr, true);
+      peak = std::max(m.arena[0].peak, m.arena[1].peak);
+    }
+    s->ws_bytes = (int64_t)(s->staging + 2 * ((peak + 255) & ~(size_t)255) + 1024);
+    s->st.resize(gs.size());
+    for (size_t i = 0; i < gs.size(); ++i) {
+      if (gs[i]->need == 0) continue;
+      s->st[i].buf = std::make_unique<DevBuf>();
+      M_HIP(hipMalloc(&s->st[i].buf->p, gs[i]->need));
+      s->st[i].cap = gs[i]->need;
+    }
+    M_HIP(hipMalloc(&s->pend.p, (size_t)B * s->cin * s->cap * H * W * sizeof(float)));
+    *out = s.release();
+    return VT_OK;
+  } catch (const Fail& f) {
+    return f.code;
+  } catch (const std::exception& e) {
+    vt_set_error("vt_session_create: %s", e.what());
+    return VT_ERR_ARG;
+  }
+}
+
+extern "C" int64_t vt_session_workspace_bytes(const vt_session* s) {
+  if (!s) {
+    vt_set_error("vt_session_workspace_bytes: null session");
+    return -1;
+  }
+  return s->ws_bytes;
+}
+
+extern "C" int vt_session_push(vt_session* s, const float* in, int32_t n, float* out, int32_t out_cap_frames, int32_t* n_out, void* workspace,
+                               int64_t workspace_bytes, vt_stream stream) {
+  try {
+    M_CHECK(s != nullptr && in != nullptr && n >= 1, "vt_session_push: bad argument (a session, and n >= 1 frames)");
+    return session_step(s, in, n, out, out_cap_frames, n_out, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, "vt_session_push");
+  } catch (const Fail& f) {
+    return f.code;                                  // SessionSwap / TileScope have put the handle's state back
+  } catch (const std::exception& e) {
+    vt_set_error("vt_session_push: %s", e.what());
+    return VT_ERR_ARG;
+  }
+}
+
+extern "C" int vt_session_finish(vt_session* s, float* out, int32_t out_cap_frames, int32_t* n_out, void* workspace, int64_t workspace_bytes,
+                                 vt_stream stream) {
+  try {
+    return session_step(s, nullptr, 0, out, out_cap_frames, n_out, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), true,
+                        "vt_session_finish");
+  } catch (const Fail& f) {
+    return f.code;
+  } catch (const std::exception& e) {
+    vt_set_error("vt_session_finish: %s", e.what());
+    return VT_ERR_ARG;
+  }
+}
+
+extern "C" int vt_session_destroy(vt_session* s) {
+  delete s;                        // hipFree of its buffers waits for the work queued on them
+  return VT_OK;
 }

@@ -216,6 +216,23 @@ class AutoencodingEngine(nn.Module):
     def _run_decoder(self, z):
         return self._gdec(z, (self.decoder.compute_dtype, getattr(self, "arith", None))) if self.use_graphs else self.decoder(z)
 
+    # ---- streaming sessions (vidtok_amd/streaming.py): the v1.1 tiling fed as the frames arrive; v1.0 / non-causal raise ---------
+    def open_encode_session(self, t_chunk_enc: Optional[int] = None):
+        from .streaming import EncodeSession
+
+        return EncodeSession(self, t_chunk_enc)
+
+    def open_decode_session(self, t_chunk_dec: Optional[int] = None, use_overlap: Optional[bool] = None, from_indices: bool = False):
+        from .streaming import DecodeSession
+
+        return DecodeSession(self, t_chunk_dec, use_overlap, from_indices)
+
+    def open_reconstruct_session(self, t_chunk_enc: Optional[int] = None, t_chunk_dec: Optional[int] = None,
+                                 use_overlap: Optional[bool] = None):
+        from .streaming import ReconstructSession
+
+        return ReconstructSession(self, t_chunk_enc, t_chunk_dec, use_overlap)
+
     # ---- checkpoints (autoencoder.py:146-176) ---------------------------------------------------
     def init_from_ckpt(self, path: str, ignore_keys=tuple(), verbose: bool = True) -> None:
         if path.endswith("ckpt"):

@@ -22,6 +22,7 @@ VT_RES_NONE, VT_RES_ADD, VT_RES_MIX = 0, 1, 2
 VT_NDHWC, VT_NCTHW = 0, 1
 VT_ACT_RELU = 1
 VT_LPIPS_CLAMP_Y, VT_LPIPS_ROUNDTRIP, VT_LPIPS_UNIT = 1, 2, 4
+VT_SESSION_ENCODE, VT_SESSION_DECODE = 0, 1
 
 
 class VtError(RuntimeError):
@@ -115,6 +116,12 @@ SIGNATURES = {
     "vt_tile_workspace_bytes": (_I64, [_P, _I32, _I32, _I32, _I32, _I32, _I32]),
     "vt_tile_encode": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
     "vt_tile_decode": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
+    "vt_session_create": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(_P)]),
+    "vt_session_workspace_bytes": (_I64, [_P]),
+    "vt_session_push": (C.c_int, [_P, _P, _I32, _P, _I32, C.POINTER(_I32), _P, _I64, _P]),
+    "vt_session_finish": (C.c_int, [_P, _P, _I32, C.POINTER(_I32), _P, _I64, _P]),
+    "vt_session_destroy": (C.c_int, [_P]),
+    "vt_copy_segments": (C.c_int, [_P, _I32, _I64, _P]),
     "vt_conv": (C.c_int, [C.POINTER(ConvDesc), _P]),
     "vt_conv_desc_size": (C.c_int, []),
     "vt_conv_work_bytes": (_I64, [C.POINTER(ConvDesc)]),

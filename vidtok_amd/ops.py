@@ -543,6 +543,28 @@ def gather_frames(src, idx, out=None, out_t0=0):
     return out
 
 
+def segment_table(pairs, device):
+    """the device table of vt_copy_segments for [(src, dst)] tensor pairs of equal byte size: int64 [n, 3] = {src address,
+    dst address, bytes} -> (table, largest segment in bytes).  Built once and reused as long as the addresses stay."""
+    rows = []
+    for src, dst in pairs:
+        nb = src.numel() * src.element_size()
+        assert nb == dst.numel() * dst.element_size() and src.is_contiguous() and dst.is_contiguous(), (src.shape, dst.shape)
+        rows.append((src.data_ptr(), dst.data_ptr(), nb))
+    table = torch.tensor(rows, dtype=torch.int64).reshape(len(rows), 3).to(device)
+    return table, max((r[2] for r in rows), default=0)
+
+
+def copy_segments(table, max_bytes):
+    """vt_copy_segments: every {src, dst, bytes} row of the device table `table` (int64 [n, 3], see segment_table) in one
+    launch on the current stream -- graph-capture safe (the table is read on the device)"""
+    _chk(table, "copy_segments.table")
+    assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 3
+    if table.shape[0] == 0:
+        return
+    L.check(L.load().vt_copy_segments(_ptr(table), table.shape[0], int(max_bytes), _stream()), "vt_copy_segments")
+
+
 def pack_conv_weight(weight, dtype, cin_stored=None, mix=None, split3=False):
     """vt_pack_conv_weight: weight fp32 [Cout, Cin, *k] on the GPU (a reference parameter) -> packed rows [Cout, ldw] for
     vt_conv: k = tap * cin_stored + c, in `dtype` (float32 / bfloat16 / float16) or, with split3, the int32-typed split-bf16 container.

@@ -658,6 +658,49 @@ int vt_lpips_tap(const void* feat, void* pooled, const float* lin_w, void* work,
 int vt_lpips_finish(const void* work, int64_t work_bytes, float* lpips, float* tap_means, int32_t N, int32_t H, int32_t W,
                     vt_stream stream);
 
+/* ---- backward building blocks (decoder fine-tuning) ---------------------------------------------------------------------
+ * vt_conv_wgrad: the weight / bias gradient of one forward convolution (vt_conv geometry):
+ *   dw[co][ci][a][p][q] = sum over output pixels (b, to, ho, wo) of dy[b][to][ho][wo][co] * x[b][ti][hi][wi][ci]
+ *     with ti = to*st - pt + a, hi = ho*sh - ph + p, wi = wo*sw - pw + q in the (ups_t / ups_s: nearest x2) up-sampled input,
+ *     zero outside it, and ti < 0 read as frame 0 under tmode VT_TPAD_REPLICATE;
+ *   db[co] = sum over output pixels of dy[..][co] (db may be NULL).
+ * x: NDHWC [B][Ti][Hi][Wi][ldx] (the stored channels; only the first Cin reach dw), dy: NDHWC [B][To][Ho][Wo][lddy], both of
+ * `dtype` (VT_F32 or VT_BF16; MFMA products, fp32 accumulation).  dw: fp32 [Cout][Cin][KT][KH][KW] (the reference's layout), db:
+ * fp32 [Cout]; both are overwritten.  The reduction over pixels is split into ranges that each write an fp32 partial tile into
+ * `work` (vt_conv_wgrad_work_bytes(d) bytes, -1 for an invalid descriptor) and a second launch adds the ranges in index order:
+ * no atomics, results are bit-reproducible and the pair is graph-capture safe.  The split depends on the shape only.
+ * Checked before any device work: VT_ERR_ARG for another dtype, tmode other than ZERO / REPLICATE, ups other than 0 / 1, an
+ * output extent the geometry cannot produce from the input ((To-1)*st + KT <= (Ti << ups_t) + pt + pt_hi, likewise H, W),
+ * more than 2^31 output pixels, or a workspace below the size asked for.
+ * ---------------------------------------------------------------------------------------------------------------------- */
+typedef struct vt_wgrad_desc {
+  const void* x;
+  const void* dy;
+  float* dw;
+  float* db;
+  void* work;
+  int64_t work_bytes;
+  int32_t B, Ti, Hi, Wi, ldx, Cin;
+  int32_t To, Ho, Wo, lddy, Cout;
+  int32_t KT, KH, KW, st, sh, sw;
+  int32_t pt, ph, pw, pt_hi, ph_hi, pw_hi;
+  int32_t tmode, ups_t, ups_s, dtype;
+} vt_wgrad_desc;
+int vt_wgrad_desc_size(void);
+int64_t vt_conv_wgrad_work_bytes(const vt_wgrad_desc* d);
+int vt_conv_wgrad(const vt_wgrad_desc* d, vt_stream stream);
+
+/* vt_layernorm_act_backward: backward of vt_layernorm_act (n = [SiLU](gamma * (y - mean) * rstd + beta) over the first C of ld
+ * channels of each of M rows).  y: the saved pre-norm rows, dn: dL/dn, both `dtype` (VT_F32 / VT_BF16) with row stride ld;
+ * mean / rstd are recomputed from y in fp32.  Writes dx = dL/dy (dx_dtype: dtype or VT_F32, row stride ldo; lanes C..ldo-1 get
+ * zeros, ldo within the 64-multiple above C), dgamma and dbeta (fp32 [C], overwritten; either may be NULL) as per-workgroup
+ * partials in `work` (vt_layernorm_act_backward_work_bytes(M, C) bytes, -1 if C > 512) added in index order by a second launch.
+ * -------------------------------------------------------------------------------------------------------------------------- */
+int64_t vt_layernorm_act_backward_work_bytes(int64_t M, int32_t C);
+int vt_layernorm_act_backward(const void* y, const void* dn, int32_t dtype, int64_t ld, void* dx, int32_t dx_dtype, int64_t ldo,
+                              const float* gamma, const float* beta, float* dgamma, float* dbeta, int64_t M, int32_t C, float eps,
+                              int32_t silu, void* work, int64_t work_bytes, vt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

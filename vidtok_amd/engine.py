@@ -57,8 +57,8 @@ class AutoencodingEngine(nn.Module):
             raise NotImplementedError("temporal tiling exists only in the v1.1 models of the reference")
         self.use_graphs = False
         # bound methods, not closures: copy.deepcopy / pickle of the engine then rebind them to the copy
-        self._genc = GraphedCall(self._encoder_fn, self._encoder_state, self._set_chunk_state)
-        self._gdec = GraphedCall(self._decoder_fn, self._decoder_state, self._set_chunk_state)
+        self._genc = GraphedCall(self._encoder_fn, self._encoder_state, self._set_chunk_state, self._encoder_version)
+        self._gdec = GraphedCall(self._decoder_fn, self._decoder_state, self._set_chunk_state, self._decoder_version)
         if verbose:
             _print0(f"[vidtok_amd.engine][AutoencodingEngine] Use ckpt_path: {ckpt_path}")
         if ckpt_path is not None:
@@ -169,6 +169,7 @@ class AutoencodingEngine(nn.Module):
         against (vidtok_amd/modules.py::_CausalState._persistent)"""
         self._genc.clear()
         self._gdec.clear()
+        self.__dict__.pop("_graph_params", None)
         self._drop_cache_buffers(self)
 
     @staticmethod
@@ -184,6 +185,21 @@ class AutoencodingEngine(nn.Module):
 
     def _decoder_fn(self, t):
         return self.decoder(t)
+
+    def _params_version(self, which):
+        """fingerprint of a sub-tree's parameters for the graph cache (graphs.py `version_fn`): the sum of their in-place
+        version counters, which only grow.  The parameter lists are collected once and dropped by invalidate_graphs."""
+        cache = self.__dict__.setdefault("_graph_params", {})
+        ps = cache.get(which)
+        if ps is None:
+            ps = cache[which] = list(getattr(self, which).parameters())
+        return sum(p._version for p in ps)
+
+    def _encoder_version(self):
+        return self._params_version("encoder")
+
+    def _decoder_version(self):
+        return self._params_version("decoder")
 
     def _encoder_state(self):
         return self._chunk_state(self.encoder)

@@ -7,9 +7,12 @@ eagerly (it also packs the weights), the second is captured into a hipGraph on a
 input into the graph's static buffer and replay.  Outputs are returned as fresh tensors (a device-to-device copy of the
 graph's static output), so the reference's "caller owns the outputs" contract holds.
 
-Opt-in (`AutoencodingEngine.enable_graphs()`): a replay does not see in-place edits of parameters made after the
-capture -- `load_state_dict`, `.to()`, `set_compute_dtype` and `enable_graphs` reset the cache, anything else needs
-`invalidate_graphs()`.  A call site keeps at most `GraphedCall.MAX_ENTRIES` shapes (least recently used out first) and its
+Opt-in (`AutoencodingEngine.enable_graphs()`): a replay runs no host code, so it would not see in-place edits of parameters
+made after the capture (the packed weight copies are refreshed only when Python asks for them).  `version_fn`, when given,
+returns a fingerprint of the parameters the function reads (their `_version` counters, which every in-place update such as
+`optimizer.step()` bumps); a call that finds it changed drops the captured graphs first.  `load_state_dict`, `.to()`,
+`set_compute_dtype` and `enable_graphs` reset the cache as well; edits that bypass the version counter (`p.data = ...`)
+need `invalidate_graphs()`.  A call site keeps at most `GraphedCall.MAX_ENTRIES` shapes (least recently used out first) and its
 graphs share one memory pool, so a process that sees many clip lengths / resolutions does not accumulate working sets.
 
 Stateful chunked passes (v1.1 temporal tiling) replay too: the modules keep their chunk-to-chunk caches in persistent
@@ -26,9 +29,11 @@ import torch
 class GraphedCall:
     MAX_ENTRIES = 12     # shapes / chunk kinds kept per call site; the least recently used one is dropped beyond that
 
-    def __init__(self, fn, state_get=None, state_set=None):
+    def __init__(self, fn, state_get=None, state_set=None, version_fn=None):
         self.fn = fn
         self.entries = {}
+        self.version_fn = version_fn
+        self._version = None
         # stateful calls: host-side state the function leaves behind (module attributes bound to cache buffers), read
         # after the capture and re-applied after every replay -- a replay runs no Python
         self.state_get, self.state_set = state_get, state_set
@@ -44,13 +49,14 @@ class GraphedCall:
     def __deepcopy__(self, memo):
         import copy
 
-        return GraphedCall(copy.deepcopy(self.fn, memo), copy.deepcopy(self.state_get, memo), copy.deepcopy(self.state_set, memo))
+        return GraphedCall(copy.deepcopy(self.fn, memo), copy.deepcopy(self.state_get, memo), copy.deepcopy(self.state_set, memo),
+                           copy.deepcopy(self.version_fn, memo))
 
     def __getstate__(self):
-        return {"fn": self.fn, "state_get": self.state_get, "state_set": self.state_set}
+        return {"fn": self.fn, "state_get": self.state_get, "state_set": self.state_set, "version_fn": self.version_fn}
 
     def __setstate__(self, st):
-        self.__init__(st["fn"], st["state_get"], st["state_set"])
+        self.__init__(st["fn"], st["state_get"], st["state_set"], st.get("version_fn"))
 
     @staticmethod
     def _is_stateful(e):
@@ -105,6 +111,11 @@ class GraphedCall:
     def __call__(self, x, key_extra=(), stateful=False, frames=None, borrow=False):
         if not self._on_device(x):
             return self.fn(x if frames is None else x[:, :, frames[0]:frames[1]].contiguous())
+        if self.version_fn is not None:
+            v = self.version_fn()
+            if v != self._version:          # parameters updated in place since the capture: the graphs replay stale weights
+                self.clear()
+                self._version = v
         x = x.contiguous()
         if frames is not None:
             x = x.float()

@@ -70,6 +70,22 @@ class TBlockDesc(C.Structure):
     )
 
 
+class WgradDesc(C.Structure):
+    """Field-for-field mirror of `vt_wgrad_desc` (include/vidtok_amd.h)."""
+
+    _fields_ = (
+        [(n, C.c_void_p) for n in ("x", "dy", "dw", "db", "work")]
+        + [("work_bytes", C.c_int64)]
+        + [(n, C.c_int32) for n in (
+            "B", "Ti", "Hi", "Wi", "ldx", "Cin",
+            "To", "Ho", "Wo", "lddy", "Cout",
+            "KT", "KH", "KW", "st", "sh", "sw",
+            "pt", "ph", "pw", "pt_hi", "ph_hi", "pw_hi",
+            "tmode", "ups_t", "ups_s", "dtype",
+        )]
+    )
+
+
 class ModelConfig(C.Structure):
     """Field-for-field mirror of `vt_model_config` (include/vidtok_amd.h)."""
 
@@ -169,6 +185,11 @@ SIGNATURES = {
     "vt_lpips_prep": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "vt_lpips_tap": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "vt_lpips_finish": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _I32, _P]),
+    "vt_wgrad_desc_size": (C.c_int, []),
+    "vt_conv_wgrad_work_bytes": (_I64, [C.POINTER(WgradDesc)]),
+    "vt_conv_wgrad": (C.c_int, [C.POINTER(WgradDesc), _P]),
+    "vt_layernorm_act_backward_work_bytes": (_I64, [_I64, _I32]),
+    "vt_layernorm_act_backward": (C.c_int, [_P, _P, _I32, _I64, _P, _I32, _I64, _P, _P, _P, _P, _I64, _I32, _F, _I32, _P, _I64, _P]),
 }
 
 _lib = None

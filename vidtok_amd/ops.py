@@ -845,3 +845,64 @@ def lpips_finish(work, n: int, h: int, w: int, tap_means: bool = False):
     taps = torch.empty((5, n), dtype=torch.float32, device=work.device) if tap_means else None
     L.check(lib.vt_lpips_finish(_ptr(work), work.numel() * work.element_size(), _ptr(out), _ptr(taps), n, h, w, _stream()), "vt_lpips_finish")
     return (out, taps) if tap_means else out
+
+
+# ---- backward building blocks (include/vidtok_amd.h: vt_conv_wgrad, vt_layernorm_act_backward) ----------------------------
+def wgrad_desc(x, dy, geom: ConvGeom, *, cin: int, cout: int, tmode=L.VT_TPAD_ZERO):
+    """vt_wgrad_desc of the weight gradient of `conv(x, ..., geom, cout=cout, tmode=tmode)` whose output gradient is dy
+    (pointers to dw / db / work left unset)"""
+    B, Ti, Hi, Wi, ldx = x.shape
+    To, Ho, Wo = geom.out_dims(Ti, Hi, Wi)
+    assert tuple(dy.shape[:4]) == (B, To, Ho, Wo) and dy.shape[4] >= cout, (tuple(dy.shape), (B, To, Ho, Wo, cout))
+    assert cin <= ldx and dy.dtype == x.dtype and x.dtype in _DT, (cin, ldx, dy.dtype, x.dtype)
+    d = L.WgradDesc()
+    d.x, d.dy = x.data_ptr(), dy.data_ptr()
+    d.B, d.Ti, d.Hi, d.Wi, d.ldx, d.Cin = B, Ti, Hi, Wi, ldx, cin
+    d.To, d.Ho, d.Wo, d.lddy, d.Cout = To, Ho, Wo, dy.shape[4], cout
+    d.KT, d.KH, d.KW, d.st, d.sh, d.sw = geom.kt, geom.kh, geom.kw, geom.st, geom.sh, geom.sw
+    d.pt, d.ph, d.pw, d.pt_hi, d.ph_hi, d.pw_hi = geom.pt, geom.ph, geom.pw, geom.pt_hi, geom.ph_hi, geom.pw_hi
+    d.tmode, d.ups_t, d.ups_s, d.dtype = tmode, geom.ups_t, geom.ups_s, _DT[x.dtype]
+    return d
+
+
+def conv_wgrad(x, dy, geom: ConvGeom, *, cin: int, cout: int, tmode=L.VT_TPAD_ZERO, bias: bool = True):
+    """(dW, db) of one convolution: x the forward input [B, Ti, Hi, Wi, ldx], dy the gradient of its output [B, To, Ho, Wo,
+    >= cout], same dtype (fp32 or bf16).  dW is fp32 in the reference's layout [cout, cin, kt, kh, kw] (stored pad channels
+    dropped), db fp32 [cout] or None.  Two launches (vt_conv_wgrad: partial tiles, fixed-order reduce): bit-reproducible."""
+    lib = L.load()
+    _chk(x, "conv_wgrad.x"); _chk(dy, "conv_wgrad.dy")
+    d = wgrad_desc(x, dy, geom, cin=cin, cout=cout, tmode=tmode)
+    dw = torch.empty((cout, cin, geom.kt, geom.kh, geom.kw), dtype=torch.float32, device=x.device)
+    db = torch.empty((cout,), dtype=torch.float32, device=x.device) if bias else None
+    nb = lib.vt_conv_wgrad_work_bytes(C.byref(d))
+    if nb < 0:
+        L.check(-1, "vt_conv_wgrad_work_bytes")
+    work = torch.empty((max(nb, 16),), dtype=torch.uint8, device=x.device)
+    d.dw, d.db, d.work, d.work_bytes = dw.data_ptr(), _ptr(db), work.data_ptr(), work.numel()
+    L.check(lib.vt_conv_wgrad(C.byref(d), _stream()), "vt_conv_wgrad")
+    return dw, db
+
+
+def layernorm_act_backward(y, dn, gamma, beta, *, silu: bool, eps: float = 1e-6, c: int = None, dx_dtype=None):
+    """Backward of layernorm_act(y, gamma, beta, silu=silu): y the saved pre-norm rows, dn the gradient of the output, both
+    [..., ld] (fp32 or bf16).  Returns (dx [..., ld] with zero pad lanes, dgamma fp32 [c], dbeta fp32 [c]); the gamma / beta
+    sums run over fixed per-workgroup partials (bit-reproducible)."""
+    lib = L.load()
+    _chk(y, "layernorm_backward.y"); _chk(dn, "layernorm_backward.dn")
+    assert dn.shape == y.shape and dn.dtype == y.dtype, (dn.shape, y.shape, dn.dtype, y.dtype)
+    ld = y.shape[-1]
+    c = c or ld
+    M = y.numel() // ld
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == c and beta.numel() == c
+    dx_dtype = dx_dtype or y.dtype
+    dx = torch.empty(y.shape, dtype=dx_dtype, device=y.device)
+    dg = torch.empty((c,), dtype=torch.float32, device=y.device)
+    dbt = torch.empty((c,), dtype=torch.float32, device=y.device)
+    nb = lib.vt_layernorm_act_backward_work_bytes(M, c)
+    if nb < 0:
+        raise L.VtError(f"vt_layernorm_act_backward: unsupported size (M={M}, C={c}; C <= 512)")
+    work = torch.empty((nb,), dtype=torch.uint8, device=y.device)
+    L.check(lib.vt_layernorm_act_backward(_ptr(y), _ptr(dn), _DT[y.dtype], ld, _ptr(dx), _DT[dx_dtype], ld, _ptr(gamma), _ptr(beta),
+                                          _ptr(dg), _ptr(dbt), M, c, float(eps), int(bool(silu)), _ptr(work), nb, _stream()),
+            "vt_layernorm_act_backward")
+    return dx, dg, dbt

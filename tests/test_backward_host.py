@@ -128,3 +128,102 @@ def test_ops_wrappers_refuse_cpu_tensors(dtype):
         ops.conv_wgrad(x, x, ops.ConvGeom(), cin=8, cout=8)
     with pytest.raises(L.VtError, match="GPU only"):
         ops.layernorm_act_backward(x, x, torch.ones(8), torch.zeros(8), silu=True)
+
+
+# ---- the harness of the decoder-site tests, checked where there is no GPU ---------------------------------------------------
+def test_edge_geometries_are_the_engines_own():
+    """the strided / phase geometries of the GPU unit grid are what the engine's modules build"""
+    import backward_sites as S
+    from vidtok_amd import modules as M
+
+    G = {k: g for k, (g, _) in S.edge_geoms().items()}
+    assert G["time-down 3x3x3 st2"] == M.TimeDownsampleResCausal2x(8, 8).conv.geom()
+    assert G["3x3x3 s222"] == M.CausalConv3d(8, 8, 3, stride=(2, 2, 2)).geom()
+    assert G["1x3x3 s21"] == M.CausalConv3d(8, 8, (1, 3, 3), stride=(1, 2, 1)).geom()
+    assert G["up_t 3x3x3"] == M.CausalConv3d(8, 8, 3).geom(1)
+    c1 = M.CausalConv1d(8, 8, 3, stride=2)
+    assert G["time-down 3x1x1 st2"] == M.ConvGeom(kt=c1.k, st=c1.stride, pt=c1.time_pad)
+    assert G["1x3x3"] == M._G3x3 and G["1x1x1"] == M._G1x1
+    assert {G[f"phase 2x2 {py}{px}"] for py in (0, 1) for px in (0, 1)} == {g for _py, _px, _pack, g in M.Upsample(8, True)._parity}
+
+
+def test_tap_by_tap_wgrad_reference_matches_autograd():
+    """backward_sites.ref_wgrad_taps (one fp64 GEMM per tap, what the large sites use) against ref_wgrad (torch autograd through
+    conv3d) on every geometry of the unit grid, both time-pad modes, odd and even extents, pad channels in x and dy"""
+    import backward_sites as S
+    from util import rel_err
+
+    gen = torch.Generator().manual_seed(1)
+    for name, (g, tmodes) in S.edge_geoms().items():
+        for dims in ((2, 3, 5, 7), (1, 4, 6, 4)):
+            x = torch.randn(dims + (8,), generator=gen)
+            dy = torch.randn((dims[0],) + g.out_dims(*dims[1:]) + (16,), generator=gen)
+            for tmode in tmodes:
+                (aw, ab), (bw, bb) = S.ref_wgrad_taps(x, dy, g, 5, 11, tmode), S.ref_wgrad(x, dy, g, 5, 11, tmode)
+                assert rel_err(aw, bw) <= 1e-12 and rel_err(ab, bb) <= 1e-12, (name, dims, tmode)
+
+
+def test_plan_rules_match_the_library(built_lib):
+    """backward_sites.wgrad_plan / ln_backward_plan restate the documented split rules; the library's work-byte queries agree on the
+    shapes of the GPU grid and on a sweep, so the GPU tests' expectations about ranges and idle workgroups hold for the build at hand"""
+    import backward_sites as S
+
+    for M in (21, 32, 2048, 32768, 32256, 16810, 2 * 17 * 256 * 256, 70, 32674):
+        for ldx, cout, taps in ((8, 8, 1), (128, 128, 27), (72, 130, 9)):
+            d = _desc(B=1, To=1, Ho=1, Wo=M, Ti=1, Hi=1, Wi=M, ldx=ldx, Cin=ldx, Cout=cout, lddy=cout, KT=1, KH=1, KW=taps, pt=0, ph=0,
+                      ph_hi=0, pw=taps - 1, pw_hi=0)
+            assert built_lib.vt_conv_wgrad_work_bytes(C.byref(d)) == S.wgrad_plan(M, taps * ldx, cout)[2], (M, ldx, cout, taps)
+    for M in (1, 3, 4, 5, 33, 4096 * 32, 4096 * 32 + 1, 4096 * 32 + 4097):
+        for c in (3, 64, 192, 512):
+            assert built_lib.vt_layernorm_act_backward_work_bytes(M, c) == S.ln_backward_plan(M, c)[3]
+
+
+@pytest.mark.parametrize("key", ["v1_0", "v1_1"])
+def test_decoder_site_table_reproduces_whole_graph_gradients(key):
+    """The site table and the geometry mapping, before any kernel is involved: for every convolution and LayerNorm site recorded in
+    one fp32 autograd pass through oracle.decoder_forward, the fp64 per-site recomputation -- from the site's recorded input and
+    output gradient, laid out and padded as the kernel would get them, with the geometry and time-pad mode the engine's modules
+    give -- equals the whole-graph weight / bias / gamma / beta gradient and the gradient of the pre-norm rows.  1e-4: fp32 autograd
+    against fp64; a wrong site, pad mode, stride or up-sampling is an error of order 1.  Every decoder parameter but the up-samplers'
+    mix factors is covered, each by exactly one site."""
+    import backward_sites as S
+    from util import rel_err
+    from vidtok_amd import lib as L
+
+    model, convs, norms, leaves = S.decoder_sites(key)
+    assert len(convs) == 65 and len(norms) == 54
+    assert all(v.grad is not None for v in leaves.values())
+    assert S.compared_parameters(convs, norms) == S.expected_parameters(leaves)
+    assert {k for k in leaves if k.endswith(".mix_factor")} == {f"decoder.up_temporal.{i}.upsample.mix_factor" for i in (1, 2)}
+    seen = set()
+    for s in convs:
+        x, dy, g, cin, cout, tmode = S.kernel_conv_operands(model, s, torch.float32)
+        assert x.shape[-1] % 8 == 0 and dy.shape[-1] % 8 == 0 and (cin, cout) == tuple(S.weight5(s.dw).shape[1::-1])
+        seen.add((g, tmode))
+        rw, rb = S.ref_wgrad_taps(x, dy, g, cin, cout, tmode)
+        assert rel_err(rw, S.weight5(s.dw)) <= 1e-4, (s.name, g, tmode, rel_err(rw, S.weight5(s.dw)))
+        if s.name.endswith(".attn_1.k.conv"):
+            # no gradient reaches the key projection's bias (softmax is blind to a shift of every key): both sides are rounding of a
+            # sum that cancels, so they are compared on the scale of its terms
+            scale = s.dy.abs().sum(dim=(0, 2, 3, 4)).max().item()
+            assert rb.abs().max().item() <= 1e-4 * scale and s.db.abs().max().item() <= 1e-4 * scale
+        else:
+            assert rel_err(rb, s.db) <= 1e-4, (s.name, rel_err(rb, s.db))
+    # what the future autograd path relies on: the causal 3-tap convolutions pad two frames in front (zeros under v1.0, the first
+    # frame under v1.1), the spatial up-sampler's convolution reads the tensor in front of the up-sampling, the temporal one too
+    # where it is nearest (v1.0) and the interpolated tensor where it is trilinear (v1.1)
+    tm = L.VT_TPAD_ZERO if key == "v1_0" else L.VT_TPAD_REPLICATE
+    by_name = {s.name: S.site_geometry(model, s) for s in convs}
+    g, t, _x = by_name["decoder.mid.block_1.conv1.conv"]
+    assert (g.kt, g.kh, g.pt, t) == (3, 3, 2, tm)
+    g, t, x = by_name["decoder.up.2.upsample.conv"]
+    assert g.ups_s == 1 and t == L.VT_TPAD_ZERO and tuple(x.shape[3:]) == (10, 12)
+    g, t, x = by_name["decoder.up_temporal.2.upsample.conv.conv"]
+    assert (g.ups_t, x.shape[2], t) == ((1, 3, tm) if key == "v1_0" else (0, 6, tm))
+    assert len(seen) == (6 if key == "v1_0" else 5)          # 3x3x3, 3x1x1, 1x3x3, 1x1x1, up_s 1x3x3 (+ up_t 3x3x3 where nearest)
+    for s in norms:
+        y, dn, gamma, beta, c = S.kernel_norm_operands(s, leaves, torch.float32)
+        rdx, rg, rb = S.ref_ln(y, dn, gamma, beta, c, s.silu, 1e-6)
+        es = (rel_err(rdx, s.dy_pre.permute(0, 2, 3, 4, 1)), rel_err(rg, s.dgamma), rel_err(rb, s.dbeta))
+        assert max(es) <= 1e-4, (s.name, s.silu, es)
+    assert sum(not s.silu for s in norms) == 1

@@ -258,7 +258,9 @@ __global__ __launch_bounds__(kLnBlock) void layernorm_act_bwd_kernel(const T* __
       d[j] = ok ? to_f32<T>(dn[row * ld + c]) : 0.f;
       s += v[j];
     }
-    const float mean = group_sum_dpp<64>(s) * invC;
+    // a true division: C * fl(1 / C) is not 1 for most C, and the mean of a constant row has to be that constant -- one ulp of it,
+    // times rstd = eps^-1/2 on such a row, is an x-hat of 1e-3 where it is 0
+    const float mean = group_sum_dpp<64>(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {

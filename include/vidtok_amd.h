@@ -658,7 +658,7 @@ int vt_lpips_tap(const void* feat, void* pooled, const float* lin_w, void* work,
 int vt_lpips_finish(const void* work, int64_t work_bytes, float* lpips, float* tap_means, int32_t N, int32_t H, int32_t W,
                     vt_stream stream);
 
-/* ---- backward building blocks (decoder fine-tuning) ---------------------------------------------------------------------
+/* ---- backward reductions (decoder fine-tuning) ---------------------------------------------------------------------------
  * vt_conv_wgrad: the weight / bias gradient of one forward convolution (vt_conv geometry):
  *   dw[co][ci][a][p][q] = sum over output pixels (b, to, ho, wo) of dy[b][to][ho][wo][co] * x[b][ti][hi][wi][ci]
  *     with ti = to*st - pt + a, hi = ho*sh - ph + p, wi = wo*sw - pw + q in the (ups_t / ups_s: nearest x2) up-sampled input,
@@ -700,6 +700,72 @@ int64_t vt_layernorm_act_backward_work_bytes(int64_t M, int32_t C);
 int vt_layernorm_act_backward(const void* y, const void* dn, int32_t dtype, int64_t ld, void* dx, int32_t dx_dtype, int64_t ldo,
                               const float* gamma, const float* beta, float* dgamma, float* dbeta, int64_t M, int32_t C, float eps,
                               int32_t silu, void* work, int64_t work_bytes, vt_stream stream);
+
+/* ---- differentiable decode: the data-gradient path (decoder fine-tuning) ------------------------------------------------------
+ * vt_conv_dgrad: dx = the gradient of a STRIDE-1 vt_conv with respect to its stored input x [B][Ti][Hi][Wi][lddx] (before a folded
+ * nearest x2 up-sampling), from dy [B][To][Ho][Wo][lddy] (dtype VT_F32 / VT_BF16; pad lanes of dy may hold any finite value).  The
+ * MACs run on vt_conv itself: dx over the virtual (up-sampled, padded) input is the convolution of dy with the weight packed by
+ * vt_pack_conv_weight_dgrad (taps flipped, Cin / Cout transposed, rows of ldw >= taps * lddy with zero pad channels) under mirrored
+ * pads (front pad K-1-p, back pad K-1-p_hi).  Plain geometries with fp32 dx are written by that launch (acc rides its residual
+ * epilogue; lanes Cin..lddx-1 of dx are NOT written then: hand in a zeroed dx where they matter).  Otherwise the convolution writes
+ * fp32 into `work` (vt_conv_dgrad_work_bytes(d) bytes; 0 = none needed, -1 = invalid descriptor) and a fold kernel finishes: under
+ * VT_TPAD_REPLICATE the pt virtual front frames add into frame 0, under ups_t / ups_s the 2 / 2 x 2 up-sampled positions add into
+ * their source pixel, then acc (dx_dtype, row stride ldacc) is added and the fp32 sum is rounded ONCE to dx_dtype (dtype or VT_F32),
+ * pad lanes zero.  A bf16 dx is therefore the rounded fp32 dx bit for bit.  No atomics; sums in a fixed order; capture-safe.
+ * Strided geometries (st, sh or sw != 1) return VT_ERR_ARG with a message: the decoders have none (their only strided
+ * convolutions are the encoder's down-samplers).  Also refused: tmode VT_TPAD_CACHE, pads >= the kernel extent, dy extents that
+ * are not the forward convolution's.
+ * vt_grad_fold: the finishing kernel on its own (src [B][rep + (T << ups_t)][H << ups_s][W << ups_s][lds], fp32 or dx_dtype) -- with
+ * rep = 0, ups_t = 1 it is the backward of a nearest x2 time up-sampling.
+ * ---------------------------------------------------------------------------------------------------------------------- */
+typedef struct vt_dgrad_desc {
+  const void* dy;
+  const void* wt;        /* vt_pack_conv_weight_dgrad rows [Cin][ldw] in `dtype` */
+  void* dx;
+  const void* acc;       /* optional: a gradient already held for x, added (dx_dtype) */
+  void* work;
+  int64_t work_bytes;
+  int32_t B, Ti, Hi, Wi, lddx, Cin;
+  int32_t To, Ho, Wo, lddy, Cout;
+  int32_t KT, KH, KW, st, sh, sw;
+  int32_t pt, ph, pw, pt_hi, ph_hi, pw_hi;
+  int32_t tmode, ups_t, ups_s, dtype, dx_dtype;
+  int32_t ldw, ldacc;
+} vt_dgrad_desc;
+int vt_dgrad_desc_size(void);
+int vt_pack_conv_weight_dgrad(const float* w, void* out, int32_t out_dtype, int32_t Cout, int32_t Cin, int32_t cout_p, int32_t KT,
+                              int32_t KH, int32_t KW, int64_t ldw, vt_stream stream);
+int64_t vt_conv_dgrad_work_bytes(const vt_dgrad_desc* d);
+int vt_conv_dgrad(const vt_dgrad_desc* d, vt_stream stream);
+int vt_grad_fold(const void* src, int32_t src_dtype, const void* acc, void* dx, int32_t dx_dtype, int32_t B, int32_t T, int32_t H, int32_t W, int32_t C,
+                 int32_t lds, int32_t lda, int32_t ldo, int32_t rep, int32_t ups_t, int32_t ups_s, vt_stream stream);
+
+/* vt_softmax_rows_backward: ds = scale * p * (dp - rowsum(dp * p)) for p = softmax(scale * s): p [rows][ldp] (dtype VT_F32 / VT_BF16),
+ *   dp fp32 [rows][cols], ds [rows][ldo] in dtype with columns cols..ldo-1 zero; a row's arithmetic is fp32.
+ * vt_transpose_batched: out[z][c][r] = in[z][r][c] (in [Z][R][ldi], first C columns; out [Z][C][ldo], columns R..ldo-1 zero): the
+ *   K-contiguous operands of the attention backward's GEMMs (dV = P^T dO, dQ = dS K, dK = dS^T Q on vt_conv's batched GEMM form).
+ * vt_upsample_mix: y = a u + (1 - a) c, a = sigmoid(*mix_factor), over the first C of ld channels of M rows (pad lanes zero): the
+ *   alpha-mix of TimeUpsampleResCausal2x as a pass of its own, so that the training forward keeps both operands.
+ * vt_upsample_mix_backward: du = a dy, dc = (1 - a) dy (pad lanes zero) and dmix[0] = a (1 - a) sum(dy (u - c)): per-workgroup fp32
+ *   partials in `work` (vt_upsample_mix_backward_work_bytes(M, ld) bytes), added in index order by a second launch.
+ * vt_time_lerp2x_backward: the adjoint of vt_time_lerp2x: dy [B][2 Ti][HWC] -> dx [B][Ti][HWC].
+ * vt_grad_ncthw_to_ndhwc: the cotangent fp32 [B][C][T][H][W] -> [B][tpad + T][H][W][ldy] with the tpad front frames (the ones a
+ *   v1.0 decode trims) and the pad lanes zero.
+ * vt_grad_add: out = a + b (fp32 sum, one rounding), the junction of a residual path with a LayerNorm's gradient.
+ * All: dtype VT_F32 or VT_BF16, no atomics, fixed summation order, capture-safe on the caller's stream. */
+int vt_softmax_rows_backward(const void* p, int64_t ldp, const float* dp, void* ds, int64_t ldo, int32_t dtype, int64_t rows,
+                             int32_t cols, float scale, vt_stream stream);
+int vt_transpose_batched(const void* in, void* out, int32_t dtype, int32_t Z, int32_t R, int32_t C, int64_t ldi, int64_t ldo,
+                         vt_stream stream);
+int vt_upsample_mix(const void* u, const void* c, const float* mix_factor, void* y, int32_t dtype, int64_t M, int32_t C, int32_t ld,
+                    vt_stream stream);
+int64_t vt_upsample_mix_backward_work_bytes(int64_t M, int32_t ld);
+int vt_upsample_mix_backward(const void* dy, const void* u, const void* c, const float* mix_factor, void* du, void* dc, float* dmix,
+                             int32_t dtype, int64_t M, int32_t C, int32_t ld, void* work, int64_t work_bytes, vt_stream stream);
+int vt_time_lerp2x_backward(const void* dy, void* dx, int32_t dtype, int32_t B, int32_t Ti, int64_t HWC, vt_stream stream);
+int vt_grad_ncthw_to_ndhwc(const float* x, void* y, int32_t out_dtype, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W,
+                           int32_t ldy, int32_t tpad, vt_stream stream);
+int vt_grad_add(const void* a, const void* b, void* out, int32_t dtype, int64_t n, vt_stream stream);
 
 #ifdef __cplusplus
 }

@@ -300,6 +300,21 @@ class AutoencodingEngine(nn.Module):
             z = self.indices_to_latent(z)
         return self._run_decoder(z)
 
+    def decode_with_grad(self, z: torch.Tensor) -> torch.Tensor:
+        """decode(z) as a differentiable call (decoder fine-tuning on a frozen encoder, the reference's `fix_encoder: true`): the same
+        fp32 NCTHW tensor, attached to the autograd graph by one torch.autograd.Function whose backward runs on the HIP kernels and
+        fills `.grad` of every `decoder.*` parameter that requires it, and of z (vidtok_amd/backward.py).  A whole clip, causal
+        LayerNorm decoders, compute dtype fp32 or bf16 (set_compute_dtype or the caller's autocast); graphs do not apply to this path.
+        Raises NotImplementedError for everything else rather than returning gradients of something else."""
+        self._sync_autocast(z)
+        if self.use_tiling:
+            raise NotImplementedError("decode_with_grad: temporal tiling / sessions have no backward (a whole clip only)")
+        if self.arith not in ("fp32", "bf16"):
+            raise NotImplementedError(f"decode_with_grad: arithmetic {self.arith!r}: the backward kernels take fp32 or bf16 operands")
+        if not hasattr(self.decoder, "forward_train"):
+            raise NotImplementedError(f"decode_with_grad: {type(self.decoder).__name__} (the non-causal family) has no backward")
+        return self.decoder.forward_train(z)
+
     @torch.no_grad()
     def forward(self, x: Any) -> Tuple[torch.Tensor, torch.Tensor, dict]:
         z, reg_log = self.encode(x, return_reg_log=True)

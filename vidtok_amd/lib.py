@@ -86,6 +86,23 @@ class WgradDesc(C.Structure):
     )
 
 
+class DgradDesc(C.Structure):
+    """Field-for-field mirror of `vt_dgrad_desc` (include/vidtok_amd.h)."""
+
+    _fields_ = (
+        [(n, C.c_void_p) for n in ("dy", "wt", "dx", "acc", "work")]
+        + [("work_bytes", C.c_int64)]
+        + [(n, C.c_int32) for n in (
+            "B", "Ti", "Hi", "Wi", "lddx", "Cin",
+            "To", "Ho", "Wo", "lddy", "Cout",
+            "KT", "KH", "KW", "st", "sh", "sw",
+            "pt", "ph", "pw", "pt_hi", "ph_hi", "pw_hi",
+            "tmode", "ups_t", "ups_s", "dtype", "dx_dtype",
+            "ldw", "ldacc",
+        )]
+    )
+
+
 class ModelConfig(C.Structure):
     """Field-for-field mirror of `vt_model_config` (include/vidtok_amd.h)."""
 
@@ -190,6 +207,19 @@ SIGNATURES = {
     "vt_conv_wgrad": (C.c_int, [C.POINTER(WgradDesc), _P]),
     "vt_layernorm_act_backward_work_bytes": (_I64, [_I64, _I32]),
     "vt_layernorm_act_backward": (C.c_int, [_P, _P, _I32, _I64, _P, _I32, _I64, _P, _P, _P, _P, _I64, _I32, _F, _I32, _P, _I64, _P]),
+    "vt_dgrad_desc_size": (C.c_int, []),
+    "vt_pack_conv_weight_dgrad": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _P]),
+    "vt_conv_dgrad_work_bytes": (_I64, [C.POINTER(DgradDesc)]),
+    "vt_conv_dgrad": (C.c_int, [C.POINTER(DgradDesc), _P]),
+    "vt_grad_fold": (C.c_int, [_P, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "vt_softmax_rows_backward": (C.c_int, [_P, _I64, _P, _P, _I64, _I32, _I64, _I32, _F, _P]),
+    "vt_transpose_batched": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I64, _I64, _P]),
+    "vt_upsample_mix": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
+    "vt_upsample_mix_backward_work_bytes": (_I64, [_I64, _I32]),
+    "vt_upsample_mix_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P, _I64, _P]),
+    "vt_time_lerp2x_backward": (C.c_int, [_P, _P, _I32, _I32, _I32, _I64, _P]),
+    "vt_grad_ncthw_to_ndhwc": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "vt_grad_add": (C.c_int, [_P, _P, _P, _I32, _I64, _P]),
 }
 
 _lib = None

@@ -836,6 +836,26 @@ class DecoderCausal3DPadding(nn.Module):
     def get_last_layer(self, **kwargs):
         return self.conv_out.conv.weight
 
+    def train_stage_modules(self):
+        """the blocks between conv_in and norm_out in execution order (vidtok_amd/backward.py)"""
+        stages = [self.mid.block_1, self.mid.attn_1, self.mid.block_2]
+        for i_level in reversed(range(self.num_resolutions)):
+            for i_block in range(self.num_res_blocks + 1):
+                stages += [self.up[i_level].block[i_block], self.up_temporal[i_level].block[i_block]]
+            if i_level in self.spatial_us:
+                stages.append(self.up[i_level].upsample)
+                if i_level in self.tempo_us:
+                    stages.append(self.up_temporal[i_level].upsample)
+        return stages
+
+    def forward_train(self, z):
+        """forward(z) attached to the autograd graph: `.backward()` fills `.grad` of every decoder parameter that requires it and of
+        z (vidtok_amd/backward.py: a recording pass of un-fused launches + the HIP backward kernels).  A whole clip, LayerNorm
+        decoders, compute dtype fp32 or bf16; everything else raises NotImplementedError."""
+        from . import backward
+
+        return backward.forward_train(self, z)
+
     @torch.no_grad()
     def forward(self, z):
         dt = self.compute_dtype

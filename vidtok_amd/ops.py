@@ -847,7 +847,7 @@ def lpips_finish(work, n: int, h: int, w: int, tap_means: bool = False):
     return (out, taps) if tap_means else out
 
 
-# ---- backward building blocks (include/vidtok_amd.h: vt_conv_wgrad, vt_layernorm_act_backward) ----------------------------
+# ---- backward reductions (include/vidtok_amd.h: vt_conv_wgrad, vt_layernorm_act_backward) -----------------------------------
 def wgrad_desc(x, dy, geom: ConvGeom, *, cin: int, cout: int, tmode=L.VT_TPAD_ZERO):
     """vt_wgrad_desc of the weight gradient of `conv(x, ..., geom, cout=cout, tmode=tmode)` whose output gradient is dy
     (pointers to dw / db / work left unset)"""
@@ -906,3 +906,179 @@ def layernorm_act_backward(y, dn, gamma, beta, *, silu: bool, eps: float = 1e-6,
                                           _ptr(dg), _ptr(dbt), M, c, float(eps), int(bool(silu)), _ptr(work), nb, _stream()),
             "vt_layernorm_act_backward")
     return dx, dg, dbt
+
+
+# ---- data-gradient path of the differentiable decode (include/vidtok_amd.h: vt_conv_dgrad and the kernels around it) ---------
+_GRAD_DT = (torch.float32, torch.bfloat16)
+
+
+def pack_conv_weight_dgrad(weight, dtype, cout_stored=None):
+    """vt_pack_conv_weight_dgrad: weight fp32 [Cout, Cin, *k] on the GPU -> the rows [Cin, taps * cout_stored] vt_conv_dgrad convolves
+    dy with: taps flipped, Cin / Cout transposed, pad channels zero; `dtype` float32 or bfloat16"""
+    lib = L.load()
+    _chk(weight, "pack_dgrad.weight")
+    assert weight.dtype == torch.float32 and weight.dim() >= 3 and dtype in _GRAD_DT
+    cout, cin = weight.shape[:2]
+    k3 = (1,) * (5 - weight.dim()) + tuple(weight.shape[2:]) if weight.dim() != 3 else (weight.shape[2], 1, 1)
+    cout_p = cout_stored or pad_channels(cout)
+    ldw = k3[0] * k3[1] * k3[2] * cout_p
+    out = torch.empty((cin, ldw), dtype=dtype, device=weight.device)
+    L.check(lib.vt_pack_conv_weight_dgrad(_ptr(weight), _ptr(out), _DT[dtype], cout, cin, cout_p, k3[0], k3[1], k3[2], ldw, _stream()),
+            "vt_pack_conv_weight_dgrad")
+    return out
+
+
+def conv_dgrad(dy, w, geom: ConvGeom, *, cin: int, cout: int, tmode=L.VT_TPAD_ZERO, acc=None, dx_dtype=None):
+    """dx of `conv(x, ..., geom, cout=cout, tmode=tmode)` with respect to its stored input x [B, Ti, Hi, Wi, pad_channels(cin)] (in
+    front of a folded nearest x2 up-sampling): dy [B, To, Ho, Wo, >= cout] fp32 or bf16, w = pack_conv_weight_dgrad(weight, dy.dtype,
+    dy.shape[-1]).  `acc` (dx's shape and dtype) is added: a residual junction costs no pass of its own.  dx_dtype: dy's (default) or
+    float32; a bf16 dx is the fp32 dx rounded once.  Stride-1 geometries only (vt_conv_dgrad)."""
+    lib = L.load()
+    _chk(dy, "conv_dgrad.dy"); _chk(w, "conv_dgrad.w")
+    if (geom.st, geom.sh, geom.sw) != (1, 1, 1):
+        raise L.VtError(f"conv_dgrad: strides {(geom.st, geom.sh, geom.sw)}: only stride-1 convolutions have a data gradient here (the decoder has no strided one)")
+    assert dy.dtype in _GRAD_DT and w.dtype == dy.dtype and dy.dim() == 5, (dy.dtype, w.dtype)
+    dx_dtype = dx_dtype or dy.dtype
+    B, To, Ho, Wo, lddy = dy.shape
+    # the input extents the forward convolution had (stride 1): inverse of ConvGeom.out_dims
+    Tv, Hv, Wv = To - geom.pt - geom.pt_hi + geom.kt - 1, Ho - geom.ph - geom.ph_hi + geom.kh - 1, Wo - geom.pw - geom.pw_hi + geom.kw - 1
+    assert Tv > 0 and Hv > 0 and Wv > 0 and Tv % (1 << geom.ups_t) == 0 and Hv % (1 << geom.ups_s) == 0 and Wv % (1 << geom.ups_s) == 0, (Tv, Hv, Wv)
+    Ti, Hi, Wi = Tv >> geom.ups_t, Hv >> geom.ups_s, Wv >> geom.ups_s
+    ldx = pad_channels(cin)
+    assert tuple(w.shape) == (cin, geom.kt * geom.kh * geom.kw * lddy), (tuple(w.shape), cin, lddy)
+    d = L.DgradDesc()
+    d.dy, d.wt = dy.data_ptr(), w.data_ptr()
+    d.B, d.Ti, d.Hi, d.Wi, d.lddx, d.Cin = B, Ti, Hi, Wi, ldx, cin
+    d.To, d.Ho, d.Wo, d.lddy, d.Cout = To, Ho, Wo, lddy, cout
+    d.KT, d.KH, d.KW, d.st, d.sh, d.sw = geom.kt, geom.kh, geom.kw, geom.st, geom.sh, geom.sw
+    d.pt, d.ph, d.pw, d.pt_hi, d.ph_hi, d.pw_hi = geom.pt, geom.ph, geom.pw, geom.pt_hi, geom.ph_hi, geom.pw_hi
+    d.tmode, d.ups_t, d.ups_s, d.dtype, d.dx_dtype = tmode, geom.ups_t, geom.ups_s, _DT[dy.dtype], _DT.get(dx_dtype, -1)
+    d.ldw = w.shape[1]
+    if acc is not None:
+        _chk(acc, "conv_dgrad.acc")
+        assert acc.dtype == dx_dtype and tuple(acc.shape) == (B, Ti, Hi, Wi, ldx), (acc.dtype, tuple(acc.shape))
+        d.acc, d.ldacc = acc.data_ptr(), ldx
+    nb = lib.vt_conv_dgrad_work_bytes(C.byref(d))
+    if nb < 0:
+        L.check(-1, "vt_conv_dgrad_work_bytes")
+    # a launch that writes dx from the convolution's epilogue leaves the pad lanes alone: they are zeroed here
+    dx = (torch.empty if (nb > 0 or ldx == cin) else torch.zeros)((B, Ti, Hi, Wi, ldx), dtype=dx_dtype, device=dy.device)
+    d.dx = dx.data_ptr()
+    work = None
+    if nb > 0:
+        work = torch.empty((nb,), dtype=torch.uint8, device=dy.device)
+        d.work, d.work_bytes = work.data_ptr(), nb
+    L.check(lib.vt_conv_dgrad(C.byref(d), _stream()), "vt_conv_dgrad")
+    return dx
+
+
+def grad_fold(src, *, ups_t=0, ups_s=0, rep=0, c=None, acc=None, out_dtype=None):
+    """vt_grad_fold: src (fp32, or out_dtype) [B, rep + (T << ups_t), H << ups_s, W << ups_s, ld] -> [B, T, H, W, ld] (the up-sampled positions and the
+    `rep` front frames summed into their source pixel, + acc, rounded once to out_dtype); ups_t = 1 alone: backward of nearest x2 in time"""
+    lib = L.load()
+    _chk(src, "grad_fold.src")
+    assert src.dtype in _GRAD_DT and src.dim() == 5
+    B, Tv, Hv, Wv, ld = src.shape
+    T, H, W = (Tv - rep) >> ups_t, Hv >> ups_s, Wv >> ups_s
+    assert rep + (T << ups_t) == Tv and (H << ups_s) == Hv and (W << ups_s) == Wv
+    out_dtype = out_dtype or src.dtype
+    assert src.dtype in (torch.float32, out_dtype)
+    out = torch.empty((B, T, H, W, ld), dtype=out_dtype, device=src.device)
+    if acc is not None:
+        _chk(acc, "grad_fold.acc")
+        assert acc.shape == out.shape and acc.dtype == out_dtype
+    L.check(lib.vt_grad_fold(_ptr(src), _DT[src.dtype], _ptr(acc), _ptr(out), _DT.get(out_dtype, -1), B, T, H, W, c or ld, ld, ld, ld, rep, ups_t, ups_s, _stream()),
+            "vt_grad_fold")
+    return out
+
+
+def softmax_rows_backward(p, dp, scale: float, cols: int = None, ld_out=None):
+    """dS of p = softmax(scale * s): p [..., ldp] (fp32 / bf16, the first `cols` columns real), dp fp32 [..., cols] -> dS [..., ld_out] in p's
+    dtype, columns past `cols` zero"""
+    lib = L.load()
+    _chk(p, "softmax_backward.p"); _chk(dp, "softmax_backward.dp")
+    cols = cols or dp.shape[-1]
+    assert dp.dtype == torch.float32 and dp.shape[-1] == cols and p.shape[:-1] == dp.shape[:-1] and p.shape[-1] >= cols and p.dtype in _GRAD_DT
+    ldo = ld_out or p.shape[-1]
+    rows = dp.numel() // cols
+    ds = torch.empty(tuple(p.shape[:-1]) + (ldo,), dtype=p.dtype, device=p.device)
+    L.check(lib.vt_softmax_rows_backward(_ptr(p), p.shape[-1], _ptr(dp), _ptr(ds), ldo, _DT[p.dtype], rows, cols, float(scale), _stream()),
+            "vt_softmax_rows_backward")
+    return ds
+
+
+def transpose_batched(x, rows: int = None, cols: int = None, ld_out=None):
+    """x [Z, R, ld] -> [Z, cols, ld_out] with out[z, c, r] = x[z, r, c] for r < rows, c < cols and zeros in the columns rows..ld_out-1"""
+    lib = L.load()
+    _chk(x, "transpose.x")
+    assert x.dim() == 3 and x.dtype in _GRAD_DT
+    Z, R, ld = x.shape
+    rows, cols = rows or R, cols or ld
+    assert rows == R and cols <= ld
+    ldo = ld_out or pad_channels(R)
+    out = torch.empty((Z, cols, ldo), dtype=x.dtype, device=x.device)
+    L.check(lib.vt_transpose_batched(_ptr(x), _ptr(out), _DT[x.dtype], Z, R, cols, ld, ldo, _stream()), "vt_transpose_batched")
+    return out
+
+
+def upsample_mix(u, c, mix_factor, ch: int = None):
+    """y = a u + (1 - a) c, a = sigmoid(mix_factor) (vt_upsample_mix): the alpha-mix of a time up-sampler as a pass of its own"""
+    lib = L.load()
+    _chk(u, "mix.u"); _chk(c, "mix.c"); _chk(mix_factor, "mix.mix_factor")
+    assert u.shape == c.shape and u.dtype == c.dtype and u.dtype in _GRAD_DT and mix_factor.dtype == torch.float32
+    ld = u.shape[-1]
+    y = torch.empty_like(u)
+    L.check(lib.vt_upsample_mix(_ptr(u), _ptr(c), _ptr(mix_factor), _ptr(y), _DT[u.dtype], u.numel() // ld, ch or ld, ld, _stream()), "vt_upsample_mix")
+    return y
+
+
+def upsample_mix_backward(dy, u, c, mix_factor, ch: int = None):
+    """backward of upsample_mix -> (du = a dy, dc = (1 - a) dy, dmix fp32 [1] = a (1 - a) sum(dy (u - c))); two launches, fixed order"""
+    lib = L.load()
+    _chk(dy, "mix_backward.dy"); _chk(u, "mix_backward.u"); _chk(c, "mix_backward.c"); _chk(mix_factor, "mix_backward.mix_factor")
+    assert dy.shape == u.shape == c.shape and dy.dtype == u.dtype == c.dtype and dy.dtype in _GRAD_DT and mix_factor.dtype == torch.float32
+    ld = dy.shape[-1]
+    M = dy.numel() // ld
+    du, dc = torch.empty_like(dy), torch.empty_like(dy)
+    dmix = torch.empty((1,), dtype=torch.float32, device=dy.device)
+    nb = lib.vt_upsample_mix_backward_work_bytes(M, ld)
+    work = torch.empty((nb,), dtype=torch.uint8, device=dy.device)
+    L.check(lib.vt_upsample_mix_backward(_ptr(dy), _ptr(u), _ptr(c), _ptr(mix_factor), _ptr(du), _ptr(dc), _ptr(dmix), _DT[dy.dtype], M, ch or ld, ld,
+                                         _ptr(work), nb, _stream()), "vt_upsample_mix_backward")
+    return du, dc, dmix
+
+
+def time_lerp2x_backward(dy, t0: int, n: int, out, out_t0: int):
+    """adjoint of time_lerp2x on a frame range: out[:, out_t0 : out_t0 + n] = lerp2x^T(dy[:, t0 : t0 + 2 n]) (one launch per clip of the batch)"""
+    lib = L.load()
+    _chk(dy, "lerp_backward.dy"); _chk(out, "lerp_backward.out")
+    assert dy.dtype == out.dtype and dy.dtype in _GRAD_DT and dy.shape[0] == out.shape[0] and tuple(dy.shape[2:]) == tuple(out.shape[2:])
+    assert 0 <= t0 and t0 + 2 * n <= dy.shape[1] and 0 <= out_t0 and out_t0 + n <= out.shape[1] and n > 0
+    fr = dy[0, 0].numel()
+    for b in range(dy.shape[0]):
+        src = C.c_void_p(dy.data_ptr() + (b * dy.shape[1] + t0) * fr * dy.element_size())
+        dst = C.c_void_p(out.data_ptr() + (b * out.shape[1] + out_t0) * fr * out.element_size())
+        L.check(lib.vt_time_lerp2x_backward(src, dst, _DT[dy.dtype], 1, n, fr, _stream()), "vt_time_lerp2x_backward")
+    return out
+
+
+def grad_ncthw_to_ndhwc(g, dtype, tpad: int = 0, ld: int = None):
+    """cotangent fp32 [B, C, T, H, W] -> [B, tpad + T, H, W, ld] in `dtype`, the tpad front frames and the pad lanes zero"""
+    lib = L.load()
+    _chk(g, "grad_ncthw_to_ndhwc.g")
+    assert g.dtype == torch.float32 and g.dim() == 5 and dtype in _GRAD_DT
+    B, Cc, T, H, W = g.shape
+    ld = ld or pad_channels(Cc)
+    y = torch.empty((B, T + tpad, H, W, ld), dtype=dtype, device=g.device)
+    L.check(lib.vt_grad_ncthw_to_ndhwc(_ptr(g), _ptr(y), _DT[dtype], B, Cc, T, H, W, ld, tpad, _stream()), "vt_grad_ncthw_to_ndhwc")
+    return y
+
+
+def grad_add(a, b):
+    """a + b (fp32 sum, one rounding): two gradients meeting at a junction"""
+    lib = L.load()
+    _chk(a, "grad_add.a"); _chk(b, "grad_add.b")
+    assert a.shape == b.shape and a.dtype == b.dtype and a.dtype in _GRAD_DT
+    out = torch.empty_like(a)
+    L.check(lib.vt_grad_add(_ptr(a), _ptr(b), _ptr(out), _DT[a.dtype], a.numel(), _stream()), "vt_grad_add")
+    return out

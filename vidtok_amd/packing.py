@@ -156,3 +156,24 @@ class PackedCache:
             b = None if bias is None else bias.detach().to(torch.float32).contiguous()
             ent = self._entries[slot] = (key, (w, b))
         return ent[1]
+
+
+class DgradPackCache:
+    """The transposed, tap-flipped rows vt_conv_dgrad convolves dy with (ops.pack_conv_weight_dgrad), cached per parameter version like
+    PackedCache: an optimizer step bumps `weight._version` and the next backward packs again.  GPU parameters only (the backward has
+    no host form)."""
+
+    def __init__(self):
+        self._entries = {}           # (dtype, cout_stored) -> (validity key, rows)
+
+    def get(self, weight: torch.nn.Parameter, dtype, cout_stored):
+        from . import ops
+
+        key = (weight.device, weight._version, weight.data_ptr())
+        slot = (dtype, cout_stored)
+        ent = self._entries.get(slot)
+        if ent is None or ent[0] != key:
+            wd = weight.detach()
+            wd = wd if wd.dtype == torch.float32 and wd.is_contiguous() else wd.float().contiguous()
+            ent = self._entries[slot] = (key, ops.pack_conv_weight_dgrad(wd, dtype, cout_stored))
+        return ent[1]

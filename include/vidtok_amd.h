@@ -220,15 +220,19 @@ int vt_conv(const vt_conv_desc* d, vt_stream stream);
  * descriptor -- never from B -- and option conv_splitk, ignoring d->work); with d->work = NULL or d->work_bytes too small the call runs unsplit.  The fp32 sum of an output
  * is then taken in another order (per tap, then over the taps): results differ from the unsplit launch by fp32 rounding. */
 int64_t vt_conv_work_bytes(const vt_conv_desc* d);
-/* What vt_conv(d) would do, without launching (no GPU needed): out8 = {pixel tile, channel tile, waves per
- * workgroup, workgroups (tiles for the persistent kernel), 1 if LayerNorm comes from the conv epilogue, kernel
- * launches of the call, kernel (0 = tile-per-workgroup implicit GEMM; weight-stationary persistent 3x3 for
- * Cin = Cout = 128 bf16: 1 = conv_ws128.hip, 8 x 16-pixel tiles on 4 waves, 3 = conv_ws2.hip, 4 x 16-pixel tiles on 8 waves; 2 = the
- * narrow-output kernel; 4 = conv_in8_kernel, the encoder's conv_in from an LDS halo patch), 1 if the 8-wave tile's epilogue goes through the LDS (coalesced rows; always with a fused LayerNorm,
- * without one for bf16 full tiles), 2 if the 128 x 128 tile runs on its 4-slot ring (option conv_deep: launches with no
- * more tiles than the device has CUs), 3 if such an LDS-epilogue launch runs as 128 x 256 half tiles on 4 waves, two workgroups
- * per CU (option conv_half256)}.  Validates `d` exactly like vt_conv.  Test / measurement aid: which kernel and
- * instantiation does a parity case exercise. */
+/* What vt_conv(d) will do, without launching (no GPU needed; validates `d` exactly like vt_conv).  vt_conv runs the plan this reports --
+ * both come from one decision -- so hosts may rely on it: whether a LayerNorm is fused (before allocating its output), which
+ * instantiation a parity case exercises, which kernel serves a layer.
+ *   out8[0..1]  pixel x channel tile         out8[2]  waves per workgroup      out8[3]  workgroups (tiles for the persistent kernel)
+ *   out8[4]     1 if the LayerNorm asked for comes from the conv kernel's epilogue (0: second launch of vt_layernorm_act, or none asked)
+ *   out8[5]     kernel launches the call performs (+ 1 for an un-fused LayerNorm, + 1 for a split-K launch's reduction when d->work is given,
+ *               2 for the split-bf16 narrow kernel's two passes)
+ *   out8[6]     kernel: 0 = tile-per-workgroup implicit GEMM (conv_igemm_glds_kernel); 2 = the narrow-output kernel (conv3d_narrow_kernel);
+ *               3 = weight-stationary persistent 3x3 for Cin = Cout = 128 in a 16-bit type (conv3x3_ws2_kernel, 4 x 16-pixel tiles on 8 waves);
+ *               4 = conv_in8_kernel, the encoder's conv_in from an LDS halo patch; 1 is reserved (a kernel that is gone)
+ *   out8[7]     1 if the epilogue goes through the LDS (coalesced rows: conv_in8; the 8-wave tile always with a fused LayerNorm, without one
+ *               for full tiles in a 16-bit type), 2 if the 128 x 128 tile runs on its 4-slot ring (option conv_deep: launches with no more
+ *               tiles than the device has CUs), else 0 */
 int vt_conv_plan(const vt_conv_desc* d, int32_t* out8);
 /* Measurement aid (scripts/conv_profile.py): vt_conv(d) on the bf16 8-wave 256 x 256 tile (no LayerNorm) with shader-clock
  * stamps at the phase boundaries of K steps 8..11 of workgroup 0: stamps_out (device, 8*4*8 uint64) = [wave][step][stamp] */

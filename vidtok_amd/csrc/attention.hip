@@ -200,13 +200,7 @@ extern "C" int vt_flash_attention(const void* q, const void* k, const void* vt, 
   const void* kern = dtype == VT_F16 ? reinterpret_cast<const void*>(&flash_attn_kernel<f16_t>) : reinterpret_cast<const void*>(&flash_attn_kernel<bf16_t>);
   const int ki = dtype == VT_F16 ? 1 : 0;
   static std::atomic<bool> attr_done[2][kMaxDevices];
-  int dev = 0;
-  VT_CHECK_HIP(hipGetDevice(&dev));
-  const bool dev_ok = dev >= 0 && dev < kMaxDevices;
-  if (!dev_ok || !attr_done[ki][dev].load(std::memory_order_acquire)) {
-    VT_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS));
-    if (dev_ok) attr_done[ki][dev].store(true, std::memory_order_release);
-  }
+  if (const int rc = vt_dynamic_lds(kern, FA_LDS, attr_done[ki])) return rc;
   // the frame index rides in grid.y (65 535 at most): more frames than that go out as slices of the batch
   for (int z0 = 0; z0 < Z; z0 += 65535) {
     const int zn = Z - z0 < 65535 ? Z - z0 : 65535;

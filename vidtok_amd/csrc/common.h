@@ -1,5 +1,7 @@
 // Shared device/host helpers for libvidtok_amd (gfx950 only).
 #pragma once
+#include <atomic>
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -44,6 +46,43 @@ void vt_set_error(const char* fmt, ...);
       return VT_ERR_HIP;                                                                \
     }                                                                                   \
   } while (0)
+
+// ---- launch state -----------------------------------------------------------------------------
+constexpr int kMaxDevices = 64;    // per-device launch state (function attributes)
+
+// Raise a kernel's dynamic-LDS limit to `bytes`, once per device: `done` is the caller's flag array [kMaxDevices] of that kernel (static,
+// zero-initialised).  The attribute is per device and setting it is a runtime call, so a launch path asks for it through here and pays
+// one hipGetDevice and one load afterwards; race-free (two first launches both set it).  A device beyond the array sets it every time.
+inline int vt_dynamic_lds(const void* kern, int bytes, std::atomic<bool>* done) {
+  int dev = 0;
+  VT_CHECK_HIP(hipGetDevice(&dev));
+  const bool dev_ok = dev >= 0 && dev < kMaxDevices;
+  if (!dev_ok || !done[dev].load(std::memory_order_acquire)) {
+    VT_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    if (dev_ok) done[dev].store(true, std::memory_order_release);
+  }
+  return VT_OK;
+}
+
+// CUs of the current device (cached per device; 256 when it cannot be asked, e.g. vt_conv_plan on a host without a GPU)
+inline int device_cus() {
+  static std::atomic<int> cus[kMaxDevices];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return 256;
+  }
+  const bool dev_ok = dev >= 0 && dev < kMaxDevices;
+  int n = dev_ok ? cus[dev].load(std::memory_order_acquire) : 0;
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+      (void)hipGetLastError();
+      n = 256;
+    }
+    if (dev_ok) cus[dev].store(n, std::memory_order_release);
+  }
+  return n;
+}
 
 // ---- scalar conversions ------------------------------------------------------------------------
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t bits16) {

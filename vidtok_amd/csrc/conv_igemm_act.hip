@@ -10,29 +10,33 @@
 namespace {
 
 template <typename MT>
-int dispatch_relu(const ConvArgs& a, hipStream_t stream) {
+int dispatch_relu(const ConvArgs& a, const IgemmVariant& v, hipStream_t stream) {
   constexpr int BK = kRowBytes / (int)sizeof(MT);
   constexpr int R = VT_ACT_RELU;
-  if (a.Cout <= 64) {
-    if (a.Cin % BK == 0) return launch_variant<MT, MT, 4, 1, 2, 2, true, 0, 2, kRowBytes, R>(a, 1, stream);
-    return launch_variant<MT, MT, 4, 1, 2, 2, false, 0, 2, kRowBytes, R>(a, 1, stream);
+  VT_CHECK_VARIANT(v.stages == 2 && v.rowb == kRowBytes);
+  if (v.tile == TILE_256x64 && v.ln256 == 0) {
+    if (v.fast) return launch_tile<MT, MT, TILE_256x64, true, 0, 2, kRowBytes, R>(a, 1, stream);
+    return launch_tile<MT, MT, TILE_256x64, false, 0, 2, kRowBytes, R>(a, 1, stream);
   }
-  VT_CHECK_ARG(a.Cin % BK == 0, "vt_conv_act: Cout=%d needs Cin a multiple of %d (got %d)", a.Cout, BK, a.Cin);
-  if (a.Cout % 256 == 0 && (a.ldy & 3) == 0) {
+  VT_CHECK_ARG(v.fast, "vt_conv_act: Cout=%d needs Cin a multiple of %d (got %d)", a.Cout, BK, a.Cin);
+  if (v.tile == TILE_256x256) {
     if constexpr (is_h16<MT>::value) {
-      if (lds256_plain_eligible(a, 1, true)) return launch_variant<MT, MT, 4, 2, 2, 4, true, 1, 2, kRowBytes, R>(a, 1, stream);
+      if (v.ln256) return launch_tile<MT, MT, TILE_256x256, true, 1, 2, kRowBytes, R>(a, 1, stream);
     }
-    return launch_variant<MT, MT, 4, 2, 2, 4, true, 0, 2, kRowBytes, R>(a, 1, stream);
+    VT_CHECK_VARIANT(v.ln256 == 0);
+    return launch_tile<MT, MT, TILE_256x256, true, 0, 2, kRowBytes, R>(a, 1, stream);
   }
-  return launch_variant<MT, MT, 2, 2, 2, 2, true, 0, 2, kRowBytes, R>(a, 1, stream);
+  VT_CHECK_VARIANT(v.tile == TILE_128x128 && v.ln256 == 0);
+  return launch_tile<MT, MT, TILE_128x128, true, 0, 2, kRowBytes, R>(a, 1, stream);
 }
 
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int vt_igemm_dispatch_relu(const void* args, int dtype, void* stream) {
+extern "C" __attribute__((visibility("hidden"))) int vt_igemm_dispatch_relu(const void* args, const void* variant, int dtype, void* stream) {
   const ConvArgs& a = *reinterpret_cast<const ConvArgs*>(args);
+  const IgemmVariant& v = *reinterpret_cast<const IgemmVariant*>(variant);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VT_F32) return dispatch_relu<float>(a, s);
-  if (dtype == VT_F16) return dispatch_relu<f16_t>(a, s);
-  return dispatch_relu<bf16_t>(a, s);
+  if (dtype == VT_F32) return dispatch_relu<float>(a, v, s);
+  if (dtype == VT_F16) return dispatch_relu<f16_t>(a, v, s);
+  return dispatch_relu<bf16_t>(a, v, s);
 }

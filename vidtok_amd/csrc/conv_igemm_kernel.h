@@ -1382,26 +1382,21 @@ int launch_variant(const ConvArgs& a_in, int nbatch, hipStream_t stream) {
     kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, false, LN256, false, 0, ACT>);
   }
   int lds_bytes = LDS;
+  // the attribute is per device: one flag per (instantiation, gather form | measurement kernel, device)
+  static std::atomic<bool> attr_done[3][kMaxDevices];
+  int ki = buf ? 1 : 0;
   if (a.prof != nullptr) {   // vt_conv_profile: the scheduled 8-wave instantiations of bf16 and split-bf16 (no LayerNorm) carry the stamps
     if constexpr (EIGHT && FAST && LN256 == 0 && ACT == 0 && (SCHED_BUF == 2 || SCHED_BUF == 5) && !std::is_same<MT, f16_t>::value &&
                   std::is_same<typename storage_of<MT>::type, TOut>::value) {
       VT_CHECK_ARG(buf, "vt_conv_profile: descriptor gather only");
       kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, true, 0, true, SCHED_BUF>);
       lds_bytes = LDS + 4096;
-      VT_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+      ki = 2;
     } else {
       VT_CHECK_ARG(false, "vt_conv_profile: only the bf16 / split-bf16 8-wave 256 x 256 tile without fused LayerNorm is instrumented");
     }
   }
-  // the attribute is per device: one flag per (instantiation, gather form, device), set race-free
-  static std::atomic<bool> attr_done[2][kMaxDevices];
-  const int ki = buf ? 1 : 0;
-  int dev = 0;
-  VT_CHECK_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= kMaxDevices || !attr_done[ki][dev].load(std::memory_order_acquire)) {
-    VT_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    if (dev >= 0 && dev < kMaxDevices) attr_done[ki][dev].store(true, std::memory_order_release);
-  }
+  if (const int rc = vt_dynamic_lds(kern, lds_bytes, attr_done[ki])) return rc;
   const long long nblk = (long long)a.m_tiles * a.n_tiles;
   VT_CHECK_ARG(nblk < (1ll << 31), "vt_conv: too many tiles (%lld)", nblk);
   void* kargs[] = {&a};
@@ -1409,39 +1404,49 @@ int launch_variant(const ConvArgs& a_in, int nbatch, hipStream_t stream) {
   return VT_OK;
 }
 
-template <typename MT, typename TOut, int WAVES_M, int WAVES_N, int TM, int TN>
-int launch_fast_or_general(const ConvArgs& a, int nbatch, hipStream_t stream) {
-  constexpr int BK = kRowBytes / (int)sizeof(MT);
-  return (a.Cin % BK) == 0 ? launch_variant<MT, TOut, WAVES_M, WAVES_N, TM, TN, true>(a, nbatch, stream)
-                           : launch_variant<MT, TOut, WAVES_M, WAVES_N, TM, TN, false>(a, nbatch, stream);
+// launch_variant of tile T: the tile's template arguments come from kTileShapes, the table vt_conv_plan reports from
+template <typename MT, typename TOut, TileKind T, bool FAST, int LN256 = 0, int STAGES = 2, int ROWB = kRowBytes, int ACT = 0>
+int launch_tile(const ConvArgs& a, int nbatch, hipStream_t stream) {
+  constexpr TileShape S = kTileShapes[T];
+  return launch_variant<MT, TOut, S.wm, S.wn, S.tm, S.tn, FAST, LN256, STAGES, ROWB, ACT>(a, nbatch, stream);
 }
 
+#define VT_CHECK_VARIANT(cond) \
+  VT_CHECK_ARG(cond, "vt_conv: no instantiation of tile %d with fast %d, ln256 %d, stages %d, row bytes %d in this arithmetic", (int)v.tile, (int)v.fast, v.ln256, v.stages, v.rowb)
 
+// the pair every tile has: two-slot ring, the tap-walk form or the general gather
+template <typename MT, typename TOut, TileKind T>
+int launch_fast_or_general(const ConvArgs& a, const IgemmVariant& v, int nbatch, hipStream_t stream) {
+  VT_CHECK_VARIANT(v.ln256 == 0 && v.stages == 2 && v.rowb == kRowBytes);
+  return v.fast ? launch_tile<MT, TOut, T, true>(a, nbatch, stream) : launch_tile<MT, TOut, T, false>(a, nbatch, stream);
+}
+
+// The instantiation the plan names (conv_decide, conv_select.h): nothing is decided here.  What a translation unit does not hold --
+// LayerNorm / LDS epilogue with results in another type, the 64-byte ring outside split-bf16 -- is an argument error.
 template <typename MT, typename TOut>
-int dispatch_tile(const ConvArgs& a, int nbatch, hipStream_t stream) {
-  switch (select_tile(a, nbatch)) {
-    case TILE_256x32: return launch_fast_or_general<MT, TOut, 4, 1, 2, 1>(a, nbatch, stream);
-    case TILE_256x64: return launch_fast_or_general<MT, TOut, 4, 1, 2, 2>(a, nbatch, stream);
+int dispatch_tile(const ConvArgs& a, const IgemmVariant& v, int nbatch, hipStream_t stream) {
+  switch (v.tile) {
+    case TILE_256x32: return launch_fast_or_general<MT, TOut, TILE_256x32>(a, v, nbatch, stream);
+    case TILE_256x64: return launch_fast_or_general<MT, TOut, TILE_256x64>(a, v, nbatch, stream);
     case TILE_256x256:                                                                           // 8 waves
       if constexpr (is_split3<MT>::value) {
-        // split-bf16: 64-byte rows (one group of 16 k-values per K step) on a 4-slot ring, schedule 5
-        if (a.Cin % 16 == 0) {
-          if (a.ln_mode != 0) return launch_variant<MT, TOut, 4, 2, 2, 4, true, 1, 4, 64>(a, nbatch, stream);
-          return launch_variant<MT, TOut, 4, 2, 2, 4, true, 0, 4, 64>(a, nbatch, stream);
+        if (v.rowb == 64) {    // 64-byte rows on a 4-slot ring, schedule 5
+          VT_CHECK_VARIANT(v.fast && v.stages == 4);
+          return v.ln256 ? launch_tile<MT, TOut, TILE_256x256, true, 1, 4, 64>(a, nbatch, stream) : launch_tile<MT, TOut, TILE_256x256, true, 0, 4, 64>(a, nbatch, stream);
         }
-        return launch_variant<MT, TOut, 4, 2, 2, 4, false>(a, nbatch, stream);
       } else if constexpr (std::is_same<MT, TOut>::value) {
-        if (a.ln_mode != 0) return launch_variant<MT, TOut, 4, 2, 2, 4, true, 1>(a, nbatch, stream);   // conv_prepare checked Cin % BK
-        // the same instantiation with ln_mode = 0: coalesced stores and residual reads (-8 % on the time up-sampler's
-        // parity convolutions, -10 % on the K = 1 024 / 1 536 layers)
-        if constexpr (is_h16<TOut>::value) {
-          if (lds256_plain_eligible(a, nbatch, true)) return launch_variant<MT, TOut, 4, 2, 2, 4, true, 1>(a, nbatch, stream);
+        if (v.ln256) {         // conv_epilogue_lds256: fused LayerNorm, or ln_mode = 0 for coalesced rows
+          VT_CHECK_VARIANT(v.fast && v.stages == 2 && v.rowb == kRowBytes);
+          return launch_tile<MT, TOut, TILE_256x256, true, 1>(a, nbatch, stream);
         }
       }
-      return launch_fast_or_general<MT, TOut, 4, 2, 2, 4>(a, nbatch, stream);
+      return launch_fast_or_general<MT, TOut, TILE_256x256>(a, v, nbatch, stream);
     default:
-      if (deep_ring_eligible(a, nbatch, (int)sizeof(MT))) return launch_variant<MT, TOut, 2, 2, 2, 2, true, 0, 4>(a, nbatch, stream);
-      return launch_fast_or_general<MT, TOut, 2, 2, 2, 2>(a, nbatch, stream);
+      if (v.stages == 4) {     // the deep ring
+        VT_CHECK_VARIANT(v.tile == TILE_128x128 && v.fast && v.ln256 == 0 && v.rowb == kRowBytes);
+        return launch_tile<MT, TOut, TILE_128x128, true, 0, 4>(a, nbatch, stream);
+      }
+      return launch_fast_or_general<MT, TOut, TILE_128x128>(a, v, nbatch, stream);
   }
 }
 

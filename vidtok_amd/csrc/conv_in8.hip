@@ -231,13 +231,7 @@ extern "C" __attribute__((visibility("hidden"))) int vt_conv_in8_launch(const vo
                                        reinterpret_cast<const void*>(&conv_in8_kernel<f16_t, false>), reinterpret_cast<const void*>(&conv_in8_kernel<f16_t, true>)};
   const int ki = (dtype == VT_F16 ? 2 : 0) + (a.tmode == VT_TPAD_REPLICATE ? 1 : 0);
   static std::atomic<bool> attr_done[4][kMaxDevices];
-  int dev = 0;
-  VT_CHECK_HIP(hipGetDevice(&dev));
-  const bool dev_ok = dev >= 0 && dev < kMaxDevices;
-  if (!dev_ok || !attr_done[ki][dev].load(std::memory_order_acquire)) {
-    VT_CHECK_HIP(hipFuncSetAttribute(kerns[ki], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (dev_ok) attr_done[ki][dev].store(true, std::memory_order_release);
-  }
+  if (const int rc = vt_dynamic_lds(kerns[ki], 160 * 1024, attr_done[ki])) return rc;
   void* kargs[] = {&a};
   VT_CHECK_HIP(hipLaunchKernel(kerns[ki], dim3((unsigned)tiles), dim3(256), kargs, lds, stream));
   return VT_OK;

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_narrow_kernel(const NarrowArgs 
 }  // namespace
 
 namespace {
-// launch geometry of a qualifying vt_conv call (narrow_eligible in conv_igemm.hip)
+// launch geometry of a qualifying vt_conv call (narrow_eligible, conv_select.h)
 long long narrow_geometry(const ConvArgs& a, NarrowArgs& n) {
   n.x = a.x; n.cache = a.cache; n.w = a.w; n.bias = a.bias; n.y = reinterpret_cast<float*>(a.y);
   n.B = a.B; n.Ti = a.Ti; n.To = a.To; n.H = a.Ho; n.W = a.Wo; n.Cout = a.Cout; n.ldw = a.ldw;
@@ -291,14 +291,9 @@ extern "C" __attribute__((visibility("hidden"))) int vt_conv_narrow_launch(const
   VT_CHECK_ARG(grid > 0 && grid < (1ll << 31), "vt_conv (narrow): grid");
   const void* kerns[4] = {reinterpret_cast<const void*>(&conv3d_narrow_kernel<0>), reinterpret_cast<const void*>(&conv3d_narrow_kernel<1>),
                           reinterpret_cast<const void*>(&conv3d_narrow_kernel<2>), reinterpret_cast<const void*>(&conv3d_narrow_kernel<0, f16_t>)};
-  static std::atomic<bool> attr_done[kMaxDevices];
-  int dev = 0;
-  VT_CHECK_HIP(hipGetDevice(&dev));
-  const bool dev_ok = dev >= 0 && dev < kMaxDevices;
-  if (!dev_ok || !attr_done[dev].load(std::memory_order_acquire)) {
-    for (const void* k : kerns) VT_CHECK_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, NW_LDS));
-    if (dev_ok) attr_done[dev].store(true, std::memory_order_release);
-  }
+  static std::atomic<bool> attr_done[4][kMaxDevices];
+  for (int k = 0; k < 4; ++k)
+    if (const int rc = vt_dynamic_lds(kerns[k], NW_LDS, attr_done[k])) return rc;
   void* kargs[] = {&n};
   if (mode != 2) {
     VT_CHECK_HIP(hipLaunchKernel(kerns[mode == 1 ? 3 : 0], dim3((unsigned)grid), dim3(256), kargs, NW_LDS, stream));

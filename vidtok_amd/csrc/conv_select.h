@@ -1,9 +1,8 @@
-// Which kernel / tile / epilogue a vt_conv call gets: the decisions shared by the dispatcher (conv_igemm.hip: vt_conv, vt_conv_plan) and
-// the per-type translation units that hold the kernel instantiations (conv_igemm_{f32,bf16,f16,x3}.hip).  Pure functions of the
-// descriptor (ConvArgs) and of the option table.
+// Which kernel / tile / epilogue / ring a vt_conv call gets.  conv_decide makes the decision ONCE per call, as a ConvPlan: vt_conv runs the
+// plan, vt_conv_plan reports it, vt_conv_work_bytes / vt_conv_profile / vt_conv_act read it (conv_igemm.hip), and the per-type translation
+// units that hold the kernel instantiations (conv_igemm_{f32,bf16,f16,x3,act}.hip) switch on its IgemmVariant.  The *_eligible predicates
+// are pure functions of the descriptor (ConvArgs) and of the option table; conv_decide is their only caller.
 #pragma once
-#include <atomic>
-
 #include "conv_common.h"
 
 namespace {
@@ -15,26 +14,6 @@ namespace {
 //                     few tiles that gives; = 128 forbids it -- lets small parity cases reach either instantiation
 inline bool conv_buf() { return vt_opt(OPT_CONV_BUF) != 0; }
 inline bool conv_tinner() { return vt_opt(OPT_CONV_TINNER) != 0; }
-
-// CUs of the current device (cached per device; 256 when it cannot be asked, e.g. vt_conv_plan on a host without a GPU)
-inline int device_cus() {
-  static std::atomic<int> cus[kMaxDevices];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return 256;
-  }
-  const bool dev_ok = dev >= 0 && dev < kMaxDevices;
-  int n = dev_ok ? cus[dev].load(std::memory_order_acquire) : 0;
-  if (n == 0) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
-      (void)hipGetLastError();
-      n = 256;
-    }
-    if (dev_ok) cus[dev].store(n, std::memory_order_release);
-  }
-  return n;
-}
 
 // conv_in8_kernel (conv_in8.hip): the encoder's conv_in in a 16-bit type
 inline bool in8_eligible(const ConvArgs& a, int nbatch, int dtype, int out_dtype, bool ln_fused, int ln_mode_asked) {
@@ -68,6 +47,15 @@ inline bool deep_ring_eligible(const ConvArgs& a, int nbatch, int elem_bytes) {
 // the 27-tap 256->256 conv when introduced); everything else keeps 128x128 with two independent workgroups
 // per CU, which cover each other's prologue / epilogue / DMA stalls (256x128 tiles measured slower).
 enum TileKind { TILE_256x32 = 0, TILE_256x64, TILE_256x256, TILE_128x128 };
+// waves along pixels / channels and 32 x 32 MFMA blocks per wave of each tile: the template arguments of its instantiations (launch_tile,
+// conv_igemm_kernel.h) and the tile dimensions vt_conv_plan reports are both read from here
+struct TileShape {
+  int wm, wn, tm, tn;
+  constexpr int bm() const { return wm * tm * 32; }
+  constexpr int bn() const { return wn * tn * 32; }
+  constexpr int waves() const { return wm * wn; }
+};
+constexpr TileShape kTileShapes[4] = {{4, 1, 2, 1}, {4, 1, 2, 2}, {4, 2, 2, 4}, {2, 2, 2, 2}};
 
 // Weight-stationary persistent kernel (conv_ws2.hip): 3x3 stride-1 pad-1 convolutions in a 16-bit type with Cin = Cout = 128 on
 // frames that tile by 8 x 16 pixels -- the nine ResnetBlock convolutions of the widest level.  Option conv_ws = 0 keeps them
@@ -121,14 +109,212 @@ inline bool lds256_plain_eligible(const ConvArgs& a, int nbatch, bool h16_io) {
          (a.ldy & 7) == 0 && (a.res_mode == VT_RES_NONE || ((a.ldr & 7) == 0 && a.Tr == a.To && a.res_tshift == 0));
 }
 
+// ---- the plan ------------------------------------------------------------------------------------------------------------------------
+// Which instantiation of conv_igemm_glds_kernel a launch gets (launch_variant's template arguments beyond the types)
+struct IgemmVariant {
+  TileKind tile;
+  bool fast;    // tap-walk form (Cin a multiple of the K step); false: the general gather
+  int ln256;    // 8-wave tile: the LDS-transposed epilogue conv_epilogue_lds256 (fused LayerNorm, or plain rows with ln_mode = 0)
+  int stages;   // ring slots: 2, or 4 (the deep ring of the 128 x 128 tile; split-bf16 on the 8-wave tile)
+  int rowb;     // bytes of K per tile row per step: kRowBytes, or 64 (split-bf16 on the 8-wave tile)
+};
+
+enum ConvKernel { CONV_IGEMM = 0, CONV_NARROW = 2, CONV_WS2 = 3, CONV_IN8 = 4 };   // out8[6] of vt_conv_plan; 1 (conv_ws128, gone) stays reserved
+
+struct ConvPlan {
+  ConvKernel kernel;
+  IgemmVariant igemm;   // CONV_IGEMM: the whole launch ...
+  IgemmVariant split;   // ... and the tap-plane launch of split-K (splitk_planes > 0): its grid.z counts as nbatch in the rules
+  int splitk_planes;    // the geometry rule only (0 = none); whether the call HAS the scratch is splitk_runs (conv_igemm.hip)
+  bool ln_fused;        // the LayerNorm the descriptor asks for comes from the conv kernel's epilogue
+  int nbatch;
+  int narrow_mode;      // CONV_NARROW: 0 bf16, 1 fp16, 2 split-bf16 (fp32 x, two passes)
+};
+
+// how many tap planes vt_conv would split `a` into (0 = no split): a 16-bit type, 3 taps in time at stride 1 or the 3 rows of a 3 x 3,
+// K long, few pixels PER CLIP, plain NDHWC rows, residual add at most; `tile` = what the unsplit launch selects
+inline int splitk_planes(const vt_conv_desc* d, const ConvArgs& a, const ConvPlan& p, TileKind tile) {
+  if (vt_opt(OPT_CONV_SPLITK) == 0 || !conv_buf()) return 0;
+  if (!vt_is_h16(d->dtype) || d->out_dtype != d->dtype || p.nbatch != 1 || p.ln_fused || a.prof != nullptr) return 0;
+  const bool by_kt = a.KT == 3 && a.st == 1, by_kh = a.KT == 1 && a.KH == 3;      // three planes: the time taps, or the rows of a 3 x 3
+  if (!(by_kt || by_kh) || a.ups_t || a.ups_s || a.out_layout != VT_NDHWC || a.yt_mul != 1 || a.ys_mul == 2) return 0;
+  if (a.Cin % 64 != 0 || a.Cout % 128 != 0 || a.ldy != a.Cout || a.KT * a.KH * a.KW * a.Cin < 4608) return 0;
+  if (a.res_mode == VT_RES_MIX || (a.res_mode == VT_RES_ADD && (a.ldr != a.Cout || a.Tr != a.To || a.res_tshift != 0))) return 0;
+  if (a.tmode == VT_TPAD_CACHE && ((long long)a.Ho * a.Wo) % 256 != 0) return 0;     // the descriptor form of the cache gather: a tile inside one frame
+  const unsigned long long xb = (unsigned long long)a.B * a.Ti * a.Hi * a.Wi * a.Cin * 2, wb = (unsigned long long)a.Cout * a.ldw * 2;
+  if (xb >= 0xFFFF0000ull || wb >= 0xFFFF0000ull) return 0;
+  if (tile != TILE_256x256 && tile != TILE_128x128) return 0;
+  // The decision is a function of ONE CLIP's geometry (To, Ho, Wo, Cout, K) and never of B: a split launch sums its tap planes in
+  // another order than a whole one, so a rule that looked at the launch's pixel count (round 4: "no more tiles than CUs") tied a
+  // clip's bits to the batch it was part of.  A clip whose pixels make no more 128 x 128 tiles than the device has CUs splits --
+  // alone it would leave every workgroup by itself on a CU walking the whole K -- whatever the batch around it.
+  const long long clip_tiles = (((long long)a.To * a.Ho * a.Wo + 127) / 128) * ((a.Cout + 127) / 128);
+  return clip_tiles <= device_cus() ? 3 : 0;
+}
+
+// vt_conv's decision, made once: argument validation, the kernel's view of the descriptor (`a`) and the plan, in the order vt_conv applies
+// it -- ws2, narrow, in8, then the implicit GEMM with its tile, variant and split-K geometry.  `prof`: vt_conv_profile's stamp buffer (the
+// rules that read a.prof see it); `act`: vt_conv_act's activation, which has its own tile rule and only the implicit GEMM (conv_igemm_act.hip)
+inline int conv_decide(const vt_conv_desc* d, ConvArgs& a, ConvPlan& p, unsigned long long* prof = nullptr, int act = 0) {
+  VT_CHECK_ARG(d != nullptr, "vt_conv: null descriptor");
+  VT_CHECK_ARG(d->x && d->w && d->y, "vt_conv: null tensor pointer");
+  VT_CHECK_ARG(d->dtype == VT_F32 || d->dtype == VT_BF16 || d->dtype == VT_F16 || d->dtype == VT_BF16X3, "vt_conv: dtype %d", d->dtype);
+  VT_CHECK_ARG((d->out_dtype == d->dtype && d->dtype != VT_BF16X3) || d->out_dtype == VT_F32, "vt_conv: out_dtype %d with dtype %d",
+               d->out_dtype, d->dtype);
+  const int vec = vt_is_h16(d->dtype) ? 8 : 4;
+  if (d->dtype == VT_BF16X3)    // split weight planes: [hi 16 x bf16 | lo 16 x bf16] per 16 k-values, K padded to the block
+    VT_CHECK_ARG(d->ldw % 32 == 0 && d->ldw >= (d->KT * d->KH * d->KW * d->Cin + 31) / 32 * 32 && d->nbatch <= 1,
+                 "vt_conv: VT_BF16X3 needs ldw = K rounded up to 32 (got %d) and nbatch 1", d->ldw);
+  VT_CHECK_ARG(d->B > 0 && d->Ti > 0 && d->Hi > 0 && d->Wi > 0 && d->Cin > 0, "vt_conv: bad input dims");
+  VT_CHECK_ARG(d->To > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0, "vt_conv: bad output dims");
+  VT_CHECK_ARG(d->Cin % vec == 0, "vt_conv: Cin=%d must be a multiple of %d (pad the channel dim)", d->Cin, vec);
+  VT_CHECK_ARG(d->KT > 0 && d->KH > 0 && d->KW > 0 && d->KT * d->KH * d->KW <= 64, "vt_conv: bad taps");
+  VT_CHECK_ARG(d->st > 0 && d->sh > 0 && d->sw > 0, "vt_conv: bad strides");
+  VT_CHECK_ARG(d->ldw >= d->KT * d->KH * d->KW * d->Cin && d->ldw % vec == 0, "vt_conv: ldw=%d", d->ldw);
+  VT_CHECK_ARG((reinterpret_cast<uintptr_t>(d->x) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->w) & 15) == 0,
+               "vt_conv: x / w must be 16-byte aligned");
+  VT_CHECK_ARG(d->ups_t == 0 || d->ups_t == 1, "vt_conv: ups_t");
+  VT_CHECK_ARG(d->ups_s == 0 || d->ups_s == 1, "vt_conv: ups_s");
+  VT_CHECK_ARG(d->tmode >= VT_TPAD_ZERO && d->tmode <= VT_TPAD_CACHE, "vt_conv: tmode %d", d->tmode);
+  if (d->tmode == VT_TPAD_CACHE && d->pt > 0) {
+    VT_CHECK_ARG(d->cache != nullptr && d->ncache >= d->pt, "vt_conv: cache mode needs cache with >= pt frames");
+    VT_CHECK_ARG(d->ups_t == 0, "vt_conv: cache mode with ups_t");
+    VT_CHECK_ARG((reinterpret_cast<uintptr_t>(d->cache) & 15) == 0, "vt_conv: cache must be 16-byte aligned");
+  }
+  VT_CHECK_ARG(d->res_mode >= VT_RES_NONE && d->res_mode <= VT_RES_MIX, "vt_conv: res_mode %d", d->res_mode);
+  if (d->res_mode != VT_RES_NONE) {
+    VT_CHECK_ARG(d->res != nullptr && d->Tr > 0 && d->ldr >= d->Cout, "vt_conv: residual operand");
+    VT_CHECK_ARG(((d->To - 1) >> d->res_tshift) < d->Tr, "vt_conv: residual time extent");
+  }
+  if (d->res_mode == VT_RES_MIX) VT_CHECK_ARG(d->mix_factor != nullptr, "vt_conv: mix_factor is null");
+  if (d->out_layout == VT_NCTHW) {
+    VT_CHECK_ARG(d->out_dtype == VT_F32, "vt_conv: NCTHW output is fp32 only");
+    VT_CHECK_ARG(d->t_trim >= 0 && d->t_trim < d->To, "vt_conv: t_trim");
+  } else {
+    VT_CHECK_ARG(d->out_layout == VT_NDHWC && d->ldy >= d->Cout, "vt_conv: ldy=%d < Cout=%d", d->ldy, d->Cout);
+  }
+  const long long M = (long long)d->B * d->To * d->Ho * d->Wo;
+  VT_CHECK_ARG(M < (1ll << 31), "vt_conv: M too large");
+  const int nbatch = d->nbatch > 0 ? d->nbatch : 1;
+  const int yt_mul = d->yt_mul > 0 ? d->yt_mul : 1;
+  if (yt_mul != 1)
+    VT_CHECK_ARG(d->out_layout == VT_NDHWC && nbatch == 1 && d->yt_off >= 0 && d->yt_off < yt_mul,
+                 "vt_conv: output frame interleave needs NDHWC, nbatch 1 and 0 <= yt_off < yt_mul");
+  const int ys_mul = d->ys_mul == 2 ? 2 : 1;
+  VT_CHECK_ARG(d->ys_mul == 0 || d->ys_mul == 1 || d->ys_mul == 2, "vt_conv: ys_mul %d", d->ys_mul);
+  if (ys_mul == 2)
+    VT_CHECK_ARG(d->out_layout == VT_NDHWC && nbatch == 1 && yt_mul == 1 && (d->ys_oh | d->ys_ow | 1) == 1,
+                 "vt_conv: output pixel interleave needs NDHWC, nbatch 1, no frame interleave, offsets in {0,1}");
+  if (d->ln_mode != 0) {
+    VT_CHECK_ARG(d->ln_mode == 1 || d->ln_mode == 2, "vt_conv: ln_mode %d", d->ln_mode);
+    VT_CHECK_ARG(d->ln_gamma && d->ln_beta && d->ln_out, "vt_conv: fused LayerNorm needs gamma, beta and ln_out");
+    VT_CHECK_ARG(d->out_layout == VT_NDHWC && nbatch == 1 && d->ldn >= d->Cout, "vt_conv: fused LayerNorm: NDHWC, nbatch 1, ldn >= Cout");
+  }
+
+  memset(&a, 0, sizeof(a));
+  a.x = (const char*)d->x; a.w = (const char*)d->w; a.bias = d->bias; a.y = (char*)d->y;
+  a.res = (const char*)d->res; a.cache = (const char*)d->cache; a.mix_factor = d->mix_factor;
+  a.B = d->B; a.Ti = d->Ti; a.Hi = d->Hi; a.Wi = d->Wi; a.Cin = d->Cin;
+  a.To = d->To; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
+  a.ldw = d->ldw; a.ldy = d->ldy;
+  a.KT = d->KT; a.KH = d->KH; a.KW = d->KW;
+  a.st = d->st; a.sh = d->sh; a.sw = d->sw;
+  a.pt = d->pt; a.ph = d->ph; a.pw = d->pw;
+  a.tmode = d->tmode; a.ncache = d->ncache;
+  a.ups_t = d->ups_t; a.ups_s = d->ups_s;
+  a.res_mode = d->res_mode; a.res_tshift = d->res_tshift;
+  a.Tr = d->res_mode != VT_RES_NONE ? d->Tr : d->To;
+  a.ldr = d->ldr;
+  // streaming (nt) stores of the LDS epilogues' rows for outputs far larger than the caches (option conv_nt_mb, MiB; 0 = never)
+  a.nt_store = (vt_opt(OPT_CONV_NT_MB) > 0 && M * d->Cout * (vt_is_h16(d->out_dtype) ? 2 : 4) >= ((long long)vt_opt(OPT_CONV_NT_MB) << 20)) ? 1 : 0;
+  a.out_layout = d->out_layout; a.t_trim = d->t_trim;
+  a.M = (int)M; a.ntaps = d->KT * d->KH * d->KW; a.K = a.ntaps * d->Cin;
+  a.ys_mul = ys_mul; a.ys_oh = d->ys_oh; a.ys_ow = d->ys_ow;
+  a.yt_mul = yt_mul;
+  a.yt_step = (long long)(yt_mul - 1) * d->Ho * d->Wo;
+  a.yt_base = (long long)(yt_mul != 1 ? d->yt_off : 0) * d->Ho * d->Wo;
+  a.fd_hw = make_fastdiv((unsigned)(d->Ho * d->Wo));
+  a.fd_wo = make_fastdiv((unsigned)d->Wo); a.fd_ho = make_fastdiv((unsigned)d->Ho); a.fd_to = make_fastdiv((unsigned)d->To);
+  a.xs_z = d->xs_z; a.ws_z = d->ws_z; a.ys_z = d->ys_z; a.rs_z = d->rs_z;
+
+  a.prof = prof;
+  p = ConvPlan{};        // CONV_IGEMM, no split, nothing fused
+  p.nbatch = nbatch;
+
+  const bool h16 = vt_is_h16(d->dtype), h16_io = h16 && d->out_dtype == d->dtype;
+  const int elem = h16 ? 2 : 4;
+  // vt_conv_act has its own tile rule (conv_igemm_act.hip holds the 256 x 64, 256 x 256 and 128 x 128 tiles only)
+  auto tile_for = [&](const ConvArgs& c, int nb) {
+    if (act == 0) return select_tile(c, nb);
+    return c.Cout <= 64 ? TILE_256x64 : (c.Cout % 256 == 0 && (c.ldy & 3) == 0) ? TILE_256x256 : TILE_128x128;
+  };
+  // the instantiation of tile `t` the implicit-GEMM kernel runs `c` in; same_type: results stored in the arithmetic's own storage type
+  auto variant = [&](const ConvArgs& c, int nb, TileKind t, bool same_type) {
+    IgemmVariant v = {t, c.Cin % (kRowBytes / elem) == 0, 0, 2, kRowBytes};
+    if (t == TILE_256x256 && d->dtype == VT_BF16X3) {
+      // split-bf16: 64-byte rows (one group of 16 k-values per K step) on a 4-slot ring
+      if (c.Cin % 16 == 0) v = {t, true, c.ln_mode != 0 ? 1 : 0, 4, 64};
+    } else if (t == TILE_256x256 && same_type) {
+      // the LayerNorm rule below checked Cin; without LayerNorm the same epilogue gives coalesced stores and residual reads (-8 % on
+      // the time up-sampler's parity convolutions, -10 % on the K = 1 024 / 1 536 layers)
+      if (c.ln_mode != 0 || (h16 && lds256_plain_eligible(c, nb, true))) v = {t, true, 1, 2, kRowBytes};
+    } else if (t == TILE_128x128 && act == 0 && deep_ring_eligible(c, nb, elem)) {
+      v = {t, true, 0, 4, kRowBytes};
+    }
+    return v;
+  };
+  const TileKind tile = tile_for(a, nbatch);
+
+  // LayerNorm inside the epilogue: the weight-stationary kernel, or the 128 x 128 tile with the LDS epilogue on full tiles spanning the channel row
+  const bool ws_ln_ok = d->ln_mode == 0 || (d->ldn == 128 && (reinterpret_cast<uintptr_t>(d->ln_out) & 15) == 0);
+  const bool use_ws = act == 0 && ws_ln_ok && ws_eligible(a, nbatch, h16_io);
+  p.ln_fused = d->ln_mode != 0 && (use_ws || (d->Cout == 128 && M % 128 == 0 && (d->ldy & 7) == 0 && (d->ldn & 7) == 0 &&
+                                              (d->res_mode == VT_RES_NONE || (d->ldr & 7) == 0) && vt_opt(OPT_CONV_LDSEPI) != 0 &&
+                                              vt_opt(OPT_CONV_FUSE_LN) != 0));
+  // ... or inside the 8-wave 256 x 256 tile's epilogue for Cout = 256 (conv_epilogue_lds256): full tiles, plain rows
+  if (d->ln_mode != 0 && !p.ln_fused && d->Cout == 256 && M % 256 == 0 && (d->dtype == VT_BF16X3 ? VT_F32 : d->dtype) == d->out_dtype && nbatch == 1 &&
+      d->Cin % (kRowBytes / elem) == 0 && (d->ldy & 7) == 0 && (d->ldn & 7) == 0 &&
+      (d->res_mode == VT_RES_NONE || (d->res_mode == VT_RES_ADD && (d->ldr & 7) == 0 && d->Tr == d->To && d->res_tshift == 0) ||
+       // alpha-mix + LayerNorm (the consumer's norm behind a time up-sampler's parity launches; option conv_tup_ln)
+       (d->res_mode == VT_RES_MIX && (d->ldr & 7) == 0 && d->Tr == d->To && d->res_tshift == 0 && vt_opt(OPT_CONV_TUP_LN) != 0)) &&
+      vt_opt(OPT_CONV_FUSE_LN256) != 0 && tile == TILE_256x256)
+    p.ln_fused = true;
+  if (p.ln_fused) {
+    a.ln_gamma = d->ln_gamma; a.ln_beta = d->ln_beta; a.ln_out = (char*)d->ln_out;
+    a.ln_mode = d->ln_mode; a.ln_keep_y = d->ln_keep_y; a.ldn = d->ldn; a.ln_eps = d->ln_eps;
+  }
+  if (d->ln_mode != 0 && !p.ln_fused)
+    VT_CHECK_ARG(yt_mul == 1 && ys_mul == 1,
+                 "vt_conv: LayerNorm of an interleaved output is only available fused (Cout = 128, full tiles)");
+
+  if (use_ws) {
+    p.kernel = CONV_WS2;
+  } else if (act == 0 && narrow_eligible(a, nbatch, d->dtype, d->out_dtype, d->ln_mode)) {
+    p.kernel = CONV_NARROW;
+    p.narrow_mode = d->dtype == VT_BF16X3 ? 2 : (d->dtype == VT_F16 ? 1 : 0);
+  } else if (act == 0 && in8_eligible(a, nbatch, d->dtype, d->out_dtype, p.ln_fused, d->ln_mode)) {
+    p.kernel = CONV_IN8;
+  } else {
+    p.igemm = variant(a, nbatch, tile, (d->dtype == VT_BF16X3 ? VT_F32 : d->dtype) == d->out_dtype);
+    p.splitk_planes = act == 0 ? splitk_planes(d, a, p, tile) : 0;
+    if (p.splitk_planes > 0) {   // the partial launch: fp32 planes, no residual, no LayerNorm (launch_splitk)
+      ConvArgs s = a;
+      s.res_mode = VT_RES_NONE;
+      s.ln_mode = 0;
+      p.split = variant(s, p.splitk_planes, tile_for(s, p.splitk_planes), false);
+    }
+  }
+  return VT_OK;
+}
 }  // namespace
 
-// the per-type translation units (conv_igemm_*.hip): tile selection + launch of the implicit-GEMM kernel; `args` = ConvArgs
-extern "C" int vt_igemm_dispatch_f32(const void* args, int nbatch, void* stream);                     // fp32 -> fp32
-extern "C" int vt_igemm_dispatch_x3(const void* args, int nbatch, void* stream);                      // split-bf16 arithmetic, fp32 storage
-extern "C" int vt_igemm_dispatch_bf16(const void* args, int nbatch, int out_f32, void* stream);       // bf16 -> bf16 | fp32
-extern "C" int vt_igemm_dispatch_f16(const void* args, int nbatch, int out_f32, void* stream);        // fp16 -> fp16 | fp32
-extern "C" int vt_igemm_dispatch_relu(const void* args, int dtype, void* stream);                   // conv_igemm_act.hip: + ReLU, in the arithmetic type
+// the per-type translation units (conv_igemm_*.hip): launch of the instantiation the plan names; `args` = ConvArgs, `variant` = IgemmVariant
+// (an instantiation the unit does not hold is VT_ERR_ARG)
+extern "C" int vt_igemm_dispatch_f32(const void* args, const void* variant, int nbatch, void* stream);                  // fp32 -> fp32
+extern "C" int vt_igemm_dispatch_x3(const void* args, const void* variant, int nbatch, void* stream);                   // split-bf16 arithmetic, fp32 storage
+extern "C" int vt_igemm_dispatch_bf16(const void* args, const void* variant, int nbatch, int out_f32, void* stream);    // bf16 -> bf16 | fp32
+extern "C" int vt_igemm_dispatch_f16(const void* args, const void* variant, int nbatch, int out_f32, void* stream);     // fp16 -> fp16 | fp32
+extern "C" int vt_igemm_dispatch_relu(const void* args, const void* variant, int dtype, void* stream);                // conv_igemm_act.hip: + ReLU, in the arithmetic type
 extern "C" int vt_ws2_launch(const void* conv_args, int dtype, void* stream);                         // conv_ws2.hip
 extern "C" int vt_conv_in8_launch(const void* conv_args, int dtype, void* stream);                    // conv_in8.hip
 extern "C" int vt_conv_narrow_launch(const void* conv_args, void* stream, int mode);                  // conv_narrow.hip (mode: 0 bf16, 1 fp16, 2 split-bf16: fp32 x, two passes)

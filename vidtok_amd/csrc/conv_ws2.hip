@@ -531,17 +531,10 @@ extern "C" __attribute__((visibility("hidden"))) int vt_ws2_launch(const void* a
   } else if (dtype == VT_F16) {
     vi += 7;
   }
-  static std::atomic<int> cus[kMaxDevices];         // 0 = not set up on that device yet; else its CU count
-  int dev = 0;
-  VT_CHECK_HIP(hipGetDevice(&dev));
-  const bool dev_ok = dev >= 0 && dev < kMaxDevices;
-  int ncu = dev_ok ? cus[dev].load(std::memory_order_acquire) : 0;
-  if (ncu == 0) {
-    for (int k = 0; k < NK; ++k) VT_CHECK_HIP(hipFuncSetAttribute(kerns[k], hipFuncAttributeMaxDynamicSharedMemorySize, W2_LDS));
-    VT_CHECK_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    if (ncu <= 0) ncu = 256;
-    if (dev_ok) cus[dev].store(ncu, std::memory_order_release);
-  }
+  static std::atomic<bool> attr_done[NK][kMaxDevices];         // every instantiation on the device's first launch
+  for (int k = 0; k < NK; ++k)
+    if (const int rc = vt_dynamic_lds(kerns[k], W2_LDS, attr_done[k])) return rc;
+  const int ncu = device_cus();
   const int ntiles = (a.Wo / W2_TW) * (a.Ho / W2_TH) * a.B * a.To;   // 4 x 16-pixel tiles (ws_eligible guarantees Ho % 8 == 0, Wo % 16 == 0)
   const int grid = ntiles < ncu ? ntiles : ncu;     // one persistent workgroup per CU (nearly all of its LDS)
   ConvArgs args_copy = a;

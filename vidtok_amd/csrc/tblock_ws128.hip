@@ -709,18 +709,11 @@ int tblock_launch(const vt_tblock_desc* d, vt_stream stream_, unsigned long long
     lds += 2048;
   }
   const void* kern = kerns2[ki];
-  // per device, once: the dynamic-LDS attribute of every instantiation and the CU count (not a per-launch runtime call)
-  static std::atomic<int> cus[kMaxDevices];
-  int dev = 0;
-  VT_CHECK_HIP(hipGetDevice(&dev));
-  int ncu = (dev >= 0 && dev < kMaxDevices) ? cus[dev].load(std::memory_order_acquire) : 0;
-  if (ncu == 0) {
-    for (int k = 0; k < NK; ++k)
-      VT_CHECK_HIP(hipFuncSetAttribute(kerns2[k], hipFuncAttributeMaxDynamicSharedMemorySize, k == 20 ? T4_LDS + 2048 : T4_LDS));
-    VT_CHECK_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    if (ncu <= 0) ncu = 256;
-    if (dev >= 0 && dev < kMaxDevices) cus[dev].store(ncu, std::memory_order_release);
-  }
+  // per device, once: the dynamic-LDS attribute of every instantiation
+  static std::atomic<bool> attr_done[NK][kMaxDevices];
+  for (int k = 0; k < NK; ++k)
+    if (const int rc = vt_dynamic_lds(kerns2[k], k == 20 ? T4_LDS + 2048 : T4_LDS, attr_done[k])) return rc;
+  const int ncu = device_cus();
   const long long ncols = (long long)d->B * (d->HW / TB_PIX);
   const int grid = ncols < ncu ? (int)ncols : ncu;
   void* kargs[] = {&a};

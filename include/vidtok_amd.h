@@ -662,6 +662,37 @@ int vt_lpips_tap(const void* feat, void* pooled, const float* lin_w, void* work,
 int vt_lpips_finish(const void* work, int64_t work_bytes, float* lpips, float* tap_means, int32_t N, int32_t H, int32_t W,
                     vt_stream stream);
 
+/* ---- differentiable LPIPS: the gradient with respect to the reconstruction (the second image of every pair) ---------------------
+ * VGG16 and the lin layers are frozen and the first image is the ground truth, so the backward runs over the N reconstruction frames
+ * (frames N..2N-1 of the forward's stack) only, from relu5_3 down: vt_lpips_tap_backward at each tap, vt_conv_dgrad (weights packed
+ * by vt_pack_conv_weight_dgrad) through each of the 13 convolutions, vt_relu_backward on the dx of a convolution whose input is a
+ * non-tap ReLU output, vt_lpips_prep_backward at the bottom.  dtype VT_F32 or VT_BF16 (VT_ERR_ARG otherwise).  No atomics, every sum
+ * in a fixed order (two runs give the same bits), no allocation, no synchronisation.
+ *
+ * vt_lpips_tap_backward: feat = relu_k [2N][H][W][C] (dtype, C in 64 / 128 / 256 / 512: f0 = frame n, f1 = frame n + N), lin_w fp32
+ *   [C], gout fp32 [N] = dL/dlpips[n], dpool [N][H/2][W/2][C] (dpool_dtype: dtype or VT_F32) = the data gradient of the next slice's
+ *   first convolution, or NULL (relu5_3).  Writes dfeat [N][H][W][C] (dtype) = dL/d(pre-activation of the tap's convolution) in one
+ *   pass: per element the fp32 sum of two terms, masked by f1 > 0 (the ReLU of the tap's own convolution), rounded once.
+ *     head term, per pixel, all fp32 (eps = 1e-10):
+ *       s_i = ||f_i||_2, u_i = f_i / (s_i + eps)
+ *       e_c = 2 gout[n] lin_w[c] (u1_c - u0_c) / (H W)
+ *       d/df1_c = e_c / (s1 + eps) - f1_c (sum_j e_j f1_j) / (s1 (s1 + eps)^2)
+ *       At s1 = 0 the second term is DEFINED as 0.  This is the one divergence from torch autograd, which returns NaN there (0/0
+ *       in the backward of sqrt); with the mask f1 > 0 the whole pixel's gradient is then 0.
+ *     pool term: dpool[n][h/2][w/2][c] goes to the FIRST maximum of f1 over the 2 x 2 window in row-major order (0,0), (0,1), (1,0),
+ *       (1,1), as F.max_pool2d's backward routes it (equal positive bf16 values do occur).  A last row or column no window covers
+ *       (odd H or W) gets the head term only.
+ * vt_relu_backward: dx[i] = y[i] > 0 ? dy[i] : 0 for i < n (n a multiple of 8): y the saved post-ReLU output (dtype), dy in dy_dtype
+ *   (dtype or VT_F32: the fp32 dx of vt_conv_dgrad, rounded here once), dx in dtype.  Bit-exact.
+ * vt_lpips_prep_backward: d [N][H][W][8] (dtype; channels 0..2 real) -> dtarget fp32 [N][3][H][W] = d[..][c] / scale[c] (a true
+ *   division): the adjoint of vt_lpips_prep with flags = 0.
+ * All tensors 16-byte aligned. */
+int vt_lpips_tap_backward(const void* feat, const float* lin_w, const float* gout, const void* dpool, int32_t dpool_dtype, void* dfeat,
+                          int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, vt_stream stream);
+int vt_relu_backward(const void* dy, int32_t dy_dtype, const void* y, void* dx, int32_t dtype, int64_t n, vt_stream stream);
+int vt_lpips_prep_backward(const void* d, int32_t dtype, const float* scale, float* dtarget, int32_t N, int32_t H, int32_t W,
+                           vt_stream stream);
+
 /* ---- backward reductions (decoder fine-tuning) ---------------------------------------------------------------------------
  * vt_conv_wgrad: the weight / bias gradient of one forward convolution (vt_conv geometry):
  *   dw[co][ci][a][p][q] = sum over output pixels (b, to, ho, wo) of dy[b][to][ho][wo][co] * x[b][ti][hi][wi][ci]

@@ -202,6 +202,9 @@ SIGNATURES = {
     "vt_lpips_prep": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "vt_lpips_tap": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "vt_lpips_finish": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _I32, _P]),
+    "vt_lpips_tap_backward": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "vt_relu_backward": (C.c_int, [_P, _I32, _P, _P, _I32, _I64, _P]),
+    "vt_lpips_prep_backward": (C.c_int, [_P, _I32, _P, _P, _I32, _I32, _I32, _P]),
     "vt_wgrad_desc_size": (C.c_int, []),
     "vt_conv_wgrad_work_bytes": (_I64, [C.POINTER(WgradDesc)]),
     "vt_conv_wgrad": (C.c_int, [C.POINTER(WgradDesc), _P]),

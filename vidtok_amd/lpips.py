@@ -9,6 +9,10 @@ frames first), every VGG16 conv + ReLU is ONE vt_conv_act launch over both image
 2 x 2 max-pool that feeds the next slice, vt_lpips_finish sums the spatial means.  Arithmetic of the convolutions: fp32 by default
 (the reference's eval without --precision autocast), `set_compute_dtype(torch.bfloat16 | torch.float16)`, or the dtype of the
 caller's torch.autocast("cuda") region (the reference's precision_scope("cuda")); the head is fp32 in every mode.
+
+`LPIPS.forward_with_grad` is the same pass attached to autograd with respect to the reconstruction, for the perceptual term of the
+reference's decoder loss (vidtok/modules/losses.py:173-176): a HIP backward (vt_lpips_tap_backward, vt_conv_dgrad, vt_relu_backward,
+vt_lpips_prep_backward) over the reconstruction frames, fp32 or bf16.  Everything else here stays under no_grad.
 """
 import os
 
@@ -169,14 +173,24 @@ class LPIPS(nn.Module):
             p = self._packs[key] = (convs, lins, shift, scale)
         return p
 
+    def _pack_dgrad(self, dtype, device):
+        """the 13 convolutions' weights as vt_conv_dgrad reads them (vt_pack_conv_weight_dgrad), cached beside the forward packs"""
+        key = ("dgrad", dtype, str(device))
+        p = self._packs.get(key)
+        if p is None:
+            p = []
+            for k, (a, b) in enumerate(SLICES):
+                s = getattr(self.net, f"slice{k + 1}")
+                for i in range(a, b):
+                    if i in VGG_CONVS:
+                        w = getattr(s, str(i)).weight.detach().to(device=device, dtype=torch.float32).contiguous()
+                        p.append(ops.pack_conv_weight_dgrad(w, dtype, cout_stored=w.shape[0]))
+            self._packs[key] = p
+        return p
+
     # ---- the pass ----------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def values(self, x, y, flags=0, tap_means=False):
-        """LPIPS of every frame pair of x, y (NCHW [N,3,H,W] or NCTHW [B,3,T,H,W], on the GPU) -> fp32 [N] (frame n = b*T + t), and the
-        per-tap spatial means [5, N] with tap_means=True.  flags: vidtok_amd.lib.VT_LPIPS_* (clamp of y, eval-loop round trip, [0,1] input)"""
-        assert x.shape == y.shape and x.dim() in (4, 5) and x.shape[1] == 3, (x.shape, y.shape)
-        dt = self._dtype_now(x)
-        self.last_dtype = dt
+    def _run(self, x, y, dt, flags=0, tap_means=False, keep=None):
+        """the launches of one pass in arithmetic `dt`; `keep` (a list) receives every convolution's post-ReLU output [2N,1,h,w,c]"""
         convs, lins, shift, scale = self._pack(dt, x.device)
         x, y = x.float().contiguous(), y.float().contiguous()
         n = x.shape[0] * (x.shape[2] if x.dim() == 5 else 1)
@@ -185,11 +199,22 @@ class LPIPS(nn.Module):
         work = torch.empty((ops.lpips_work_bytes(n, H, W) // 4,), dtype=torch.float32, device=x.device)
         for idx, w, b, cout in convs:
             h = ops.conv_act(h, w, b, _GEOM3, cout=cout)
+            if keep is not None:
+                keep.append(h)
             if idx in TAP_AFTER:
                 k = TAP_AFTER[idx]
                 pooled = ops.lpips_tap(h[:, 0], lins[k], work, k, pool=k < 4)
                 h = pooled.unsqueeze(1) if pooled is not None else None
         return ops.lpips_finish(work, n, H, W, tap_means=tap_means)
+
+    @torch.no_grad()
+    def values(self, x, y, flags=0, tap_means=False):
+        """LPIPS of every frame pair of x, y (NCHW [N,3,H,W] or NCTHW [B,3,T,H,W], on the GPU) -> fp32 [N] (frame n = b*T + t), and the
+        per-tap spatial means [5, N] with tap_means=True.  flags: vidtok_amd.lib.VT_LPIPS_* (clamp of y, eval-loop round trip, [0,1] input)"""
+        assert x.shape == y.shape and x.dim() in (4, 5) and x.shape[1] == 3, (x.shape, y.shape)
+        dt = self._dtype_now(x)
+        self.last_dtype = dt
+        return self._run(x, y, dt, flags, tap_means)
 
     def forward(self, input, target):
         """reference LPIPS.forward: NCHW images in [-1, 1] -> [N, 1, 1, 1]"""
@@ -202,3 +227,59 @@ class LPIPS(nn.Module):
         assert x.dim() == 5
         flags = (L.VT_LPIPS_CLAMP_Y | L.VT_LPIPS_ROUNDTRIP) if eval_loop else 0
         return self.values(x, y, flags).reshape(x.shape[0], x.shape[2])
+
+    # ---- the differentiable pass (decoder fine-tuning) -----------------------------------------------------------------
+    def forward_with_grad(self, input, target):
+        """`forward(input, target)` attached to autograd with respect to `target` (the reconstruction): the same launches and the same
+        bits, with every convolution's post-ReLU output kept for a backward on the HIP kernels (vt_lpips_tap_backward, vt_conv_dgrad,
+        vt_relu_backward, vt_lpips_prep_backward) over the N reconstruction frames.  `input` is the ground truth and gets no gradient;
+        VGG16 and the lin layers are frozen.  fp32 or bf16 arithmetic; NCHW [N,3,H,W] only.  A target that does not require grad gets
+        the plain value."""
+        if input.dim() != 4 or target.dim() != 4:
+            raise NotImplementedError(f"LPIPS.forward_with_grad: {input.dim()}-D input: NCHW [N,3,H,W] images only (flatten a clip's frames first)")
+        dt = self._dtype_now(input)
+        if dt not in (torch.float32, torch.bfloat16):
+            raise NotImplementedError(f"LPIPS.forward_with_grad: compute dtype {dt}: the backward kernels take float32 or bfloat16 (fp16 has no loss scaling here)")
+        if input.requires_grad:
+            raise NotImplementedError("LPIPS.forward_with_grad: input.requires_grad: the gradient is taken with respect to target only (input is the ground truth)")
+        if target.dtype != torch.float32 or input.shape != target.shape or input.shape[1] != 3:
+            raise TypeError(f"LPIPS.forward_with_grad: fp32 [N,3,H,W] pairs of one shape, got {tuple(input.shape)} and {tuple(target.shape)} {target.dtype}")
+        for name, t in (("input", input), ("target", target)):
+            if not t.is_cuda:
+                raise L.VtError(f"LPIPS.forward_with_grad.{name}: tensor is on {t.device}; vidtok_amd runs on the GPU only (no CPU fallback)")
+        if not (torch.is_grad_enabled() and target.requires_grad):
+            return self.forward(input, target)
+        return _LpipsFunction.apply(self, dt, input, target)
+
+    def _backward(self, tape, cot):
+        """d(sum(cot * lpips)) / d target, fp32 NCHW: from relu5_3 down over the reconstruction half of the kept features"""
+        dt, n, feats = tape
+        dev = feats[0].device
+        _, lins, _, scale = self._pack(dt, dev)
+        wts = self._pack_dgrad(dt, dev)
+        gout = cot.reshape(-1).float().contiguous()
+        d = None                                    # fp32 gradient at the output of the convolution below (through the pool at a tap)
+        for (idx, (cin, cout)), y, wt in reversed(list(zip(VGG_CONVS.items(), feats, wts))):
+            if idx in TAP_AFTER:
+                dpre = ops.lpips_tap_backward(y[:, 0], lins[TAP_AFTER[idx]], gout, dpool=None if d is None else d[:, 0]).unsqueeze(1)
+            else:
+                dpre = ops.relu_backward(d, y[n:])
+            d = ops.conv_dgrad(dpre, wt, _GEOM3, cin=cin, cout=cout, dx_dtype=torch.float32)
+        return ops.lpips_prep_backward(d[:, 0], scale)
+
+
+class _LpipsFunction(torch.autograd.Function):
+    """LPIPS.forward_with_grad as one autograd node: inputs (input, target), output [N,1,1,1]; gradient to target only"""
+
+    @staticmethod
+    def forward(ctx, mod, dt, input, target):
+        mod.last_dtype = dt
+        feats = []
+        val = mod._run(input, target, dt, keep=feats)
+        ctx.mod, ctx.tape = mod, (dt, input.shape[0], feats)
+        return val.reshape(-1, 1, 1, 1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, cot):
+        return None, None, None, ctx.mod._backward(ctx.tape, cot)

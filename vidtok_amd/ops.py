@@ -1082,3 +1082,45 @@ def grad_add(a, b):
     out = torch.empty_like(a)
     L.check(lib.vt_grad_add(_ptr(a), _ptr(b), _ptr(out), _DT[a.dtype], a.numel(), _stream()), "vt_grad_add")
     return out
+
+
+# ---- differentiable LPIPS (include/vidtok_amd.h: vt_lpips_tap_backward, vt_relu_backward, vt_lpips_prep_backward) ---------------------
+def lpips_tap_backward(feat, lin_w, gout, dpool=None):
+    """vt_lpips_tap_backward over relu_k feat [2N, H, W, C] (fp32 or bf16): gout fp32 [N] the gradient of every pair's LPIPS, dpool
+    [N, H/2, W/2, C] (feat's dtype or fp32) the gradient of the pooled rows or None -> dfeat [N, H, W, C], the gradient at the
+    pre-activation of the tap's convolution for the reconstruction frames (head + pool routing + ReLU mask, one rounding)"""
+    lib = L.load()
+    _chk(feat, "lpips_tap_backward.feat"); _chk(lin_w, "lpips_tap_backward.lin_w"); _chk(gout, "lpips_tap_backward.gout")
+    assert feat.dim() == 4 and feat.shape[0] % 2 == 0 and feat.dtype in _GRAD_DT, (tuple(feat.shape), feat.dtype)
+    n2, H, W, Cc = feat.shape
+    n = n2 // 2
+    assert lin_w.dtype == torch.float32 and lin_w.numel() == Cc and gout.dtype == torch.float32 and gout.numel() == n
+    if dpool is not None:
+        _chk(dpool, "lpips_tap_backward.dpool")
+        assert tuple(dpool.shape) == (n, H // 2, W // 2, Cc) and dpool.dtype in (feat.dtype, torch.float32), (tuple(dpool.shape), dpool.dtype)
+    dfeat = torch.empty((n, H, W, Cc), dtype=feat.dtype, device=feat.device)
+    L.check(lib.vt_lpips_tap_backward(_ptr(feat), _ptr(lin_w), _ptr(gout), _ptr(dpool), _DT[dpool.dtype] if dpool is not None else -1, _ptr(dfeat),
+                                      _DT[feat.dtype], n, H, W, Cc, _stream()), "vt_lpips_tap_backward")
+    return dfeat
+
+
+def relu_backward(dy, y):
+    """vt_relu_backward: dy * (y > 0) in y's dtype (fp32 or bf16); y the saved post-ReLU output, dy of y's shape in y's dtype or fp32
+    (rounded once)"""
+    lib = L.load()
+    _chk(dy, "relu_backward.dy"); _chk(y, "relu_backward.y")
+    assert dy.shape == y.shape and y.dtype in _GRAD_DT and dy.dtype in (y.dtype, torch.float32), (tuple(dy.shape), tuple(y.shape), dy.dtype, y.dtype)
+    dx = torch.empty_like(y)
+    L.check(lib.vt_relu_backward(_ptr(dy), _DT[dy.dtype], _ptr(y), _ptr(dx), _DT[y.dtype], y.numel(), _stream()), "vt_relu_backward")
+    return dx
+
+
+def lpips_prep_backward(d, scale):
+    """vt_lpips_prep_backward: d [N, H, W, 8] (fp32 or bf16, 3 real channels) -> fp32 NCHW [N, 3, H, W] = d / scale"""
+    lib = L.load()
+    _chk(d, "lpips_prep_backward.d"); _chk(scale, "lpips_prep_backward.scale")
+    assert d.dim() == 4 and d.shape[3] == 8 and d.dtype in _GRAD_DT and scale.dtype == torch.float32 and scale.numel() == 3
+    N, H, W, _ = d.shape
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=d.device)
+    L.check(lib.vt_lpips_prep_backward(_ptr(d), _DT[d.dtype], _ptr(scale), _ptr(out), N, H, W, _stream()), "vt_lpips_prep_backward")
+    return out

@@ -1,14 +1,18 @@
 """Differentiable decode on one MI355X: decode, training forward, backward, peak memory, and the backward split by kernel class.
 
     python scripts/decoder_backward_bench.py [--model vidtok_kl_causal_488_4chn] [--frames 17] [--size 256] [--reps 5] [--out profiles/decoder_backward.md]
+    python scripts/decoder_backward_bench.py --recompute none,norms,stages --batch 1,4          (the activation-recomputation table alone)
 
 vidtok_kl_causal_488_4chn, B = 1, 17 x 256 x 256, in bf16 and fp32.  Times are medians of `--reps` device-synchronised calls after a
 warm-up.  The per-class split comes from event timing: every `ops.*` call of one backward is bracketed by HIP events (the calls are
 stream-ordered, so the brackets add up to the whole), classes = dgrad (vt_conv_dgrad: convolution over dy + fold), wgrad
 (vt_conv_wgrad + its reduce), LayerNorm backward, attention (GEMMs, softmax backward, transposes), glue (mix, folds, adds, layout).
+`--recompute` adds the axis of `decode_with_grad(z, recompute=...)`: per batch size, dtype and mode the training forward, the backward,
+the bytes the tape holds between the two (`backward.tape_bytes`) and the peak of forward + backward above the resident model and batch.
 Not part of bench.py.
 """
 import argparse
+import gc
 import os
 import statistics
 import sys
@@ -80,6 +84,47 @@ def split_backward(model, z, x):
     return per_class, per_layer
 
 
+def recompute_table(args, modes, batches):
+    """one row per (batch, dtype, mode); time and memory also as a ratio to recompute="none" of the same run when that is among the modes"""
+    from util import build_model
+    from vidtok_amd import backward
+
+    lines = [f"## activation recomputation: {args.model}, {args.frames} x {args.size} x {args.size} (scripts/decoder_backward_bench.py --recompute, medians of {args.reps})", "",
+             "| B | dtype | recompute | training forward ms | backward ms | tape GiB | peak memory of forward + backward GiB | backward / none | peak / none |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for B in batches:
+        x = (torch.rand((B, 3, args.frames, args.size, args.size), generator=torch.Generator().manual_seed(0)) * 2 - 1).to("cuda:0")
+        for dtype in (torch.bfloat16, torch.float32):
+            model, _cfg, _sd = build_model(args.model, seed=7, device="cuda:0", dtype=dtype)
+            zg = model.encode(x).clone().requires_grad_(True)
+            base_row = None
+            for mode in modes:
+                def step():
+                    for p in model.decoder.parameters():
+                        p.grad = None
+                    zg.grad = None
+                    torch.nn.functional.mse_loss(model.decode_with_grad(zg, recompute=mode), x).backward()
+
+                t_fwd = timed(lambda: model.decode_with_grad(zg, recompute=mode), args.reps)
+                t_bwd = timed(step, args.reps) - t_fwd
+                tape = backward.tape_bytes(backward.train_forward(model.decoder, zg, mode)[1]) / 2 ** 30
+                gc.collect()
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                step()
+                torch.cuda.synchronize()
+                peak = (torch.cuda.max_memory_allocated() - base) / 2 ** 30
+                if mode == "none":
+                    base_row = (t_bwd, peak)
+                rel = ("-", "-") if base_row is None else (f"{t_bwd / base_row[0]:.3f}", f"{peak / base_row[1]:.3f}")
+                lines.append(f"| {B} | {str(dtype).replace('torch.', '')} | {mode} | {t_fwd:.2f} | {t_bwd:.2f} | {tape:.2f} | {peak:.2f} | {rel[0]} | {rel[1]} |")
+                print(lines[-1], flush=True)
+            del model, zg
+            torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="vidtok_kl_causal_488_4chn")
@@ -87,8 +132,19 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--recompute", default=None, help="comma-separated modes of decode_with_grad(z, recompute=...): the recomputation table instead of the default report")
+    ap.add_argument("--batch", default="1", help="comma-separated batch sizes of the recomputation table")
     args = ap.parse_args()
     from util import build_model
+
+    if args.recompute:
+        text = "\n".join(recompute_table(args, args.recompute.split(","), [int(b) for b in args.batch.split(",")])) + "\n"
+        print(text)
+        if args.out:                     # a section of its own: added to the end of the file, whatever it already holds stays
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(("\n" if os.path.getsize(args.out) else "") + text)
+        return
 
     lines = [f"## {args.model}, B = 1, {args.frames} x {args.size} x {args.size} (scripts/decoder_backward_bench.py, medians of {args.reps})", ""]
     x = (torch.rand((1, 3, args.frames, args.size, args.size), generator=torch.Generator().manual_seed(0)) * 2 - 1).to("cuda:0")

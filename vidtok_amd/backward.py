@@ -16,10 +16,17 @@ The backward walks the stages in reverse.  Data gradients: `ops.conv_dgrad` (the
 transposed, tap-flipped weight; `acc=` adds the gradient already held at a junction); parameter gradients: `ops.conv_wgrad`,
 `ops.layernorm_act_backward`, `ops.upsample_mix_backward`.  Nothing uses float atomics: two runs give the same bits.
 
+`recompute=` trades tape for arithmetic (activation recomputation).  "none" keeps everything listed above.  "norms" drops the output
+of every LayerNorm(+SiLU) and rebuilds it from the saved pre-norm rows right before the weight gradient that reads it.  "stages" keeps
+only the latent rows, the input of every stage and the tensor in front of norm_out; the backward re-runs one stage's forward at a time.
+Both rebuild with the forward's launches on the forward's operands in the tape's dtype, so every result has the bits of "none"; a
+decoder parameter changed in place between forward and backward would be repacked and silently change them, so that is an error.
+
 A whole clip only (first-chunk form: zero pad for v1.0, first-frame replicate for v1.1; the chunk caches are neither read nor
 written), `norm_type: layernorm`, compute dtype fp32 or bf16.
 """
 import dataclasses
+import typing
 
 import torch
 
@@ -27,7 +34,15 @@ from . import lib as L
 from . import modules as M
 from . import ops
 from .ops import ConvGeom
+from . import packing
 from .packing import DgradPackCache, PackedCache
+
+RECOMPUTE_MODES = ("none", "norms", "stages")
+
+
+def check_recompute(recompute):
+    if recompute not in RECOMPUTE_MODES:
+        raise ValueError(f"decode_with_grad: recompute={recompute!r}: one of {RECOMPUTE_MODES}")
 
 
 @dataclasses.dataclass
@@ -61,9 +76,14 @@ def _wants(p):
     return p is not None and p.requires_grad
 
 
+def _reads_input(s: _Site):
+    """does the backward of this convolution read its input (vt_conv_wgrad does; vt_conv_dgrad reads the weight only)"""
+    return _wants(s.conv.weight) or _wants(s.conv.bias)
+
+
 def _conv_backward(s: _Site, x, dy, grads, acc=None, need_dx=True):
     """parameter gradients of one convolution into `grads`; returns dx (+ acc), or None when nobody asks for it"""
-    if _wants(s.conv.weight) or _wants(s.conv.bias):
+    if _reads_input(s):
         dw, db = ops.conv_wgrad(x, dy, s.geom, cin=s.cin, cout=s.cout, tmode=s.tmode, bias=s.conv.bias is not None)
         grads[s.conv.weight] = dw.view(s.conv.weight.shape)
         if s.conv.bias is not None:
@@ -86,8 +106,14 @@ def _norm_backward(norm, y, dn, silu, grads):
     return dx
 
 
-# ---- stages: forward(x) -> (y, saved), backward(saved, dy, grads) -> dx ------------------------------------------------------
-class _ResStage:
+# ---- stages: forward(x, dt) -> (y, saved), backward(saved, dy, grads, dt) -> dx; lean(saved) = saved without what recompute="norms"
+# rebuilds (a None in the place of a LayerNorm output: backward runs the forward's _norm call again, in the tape's dt) -----------------
+class _Stage:
+    def lean(self, saved):
+        return saved
+
+
+class _ResStage(_Stage):
     """ResnetBlock / ResnetCausalBlock / ResnetCausalBlock1D: LN-SiLU-conv LN-SiLU-conv (+ shortcut conv) + x"""
 
     def __init__(self, blk):
@@ -106,18 +132,28 @@ class _ResStage:
         sc = x if self.nin is None else _conv(self.nin, x, dt)
         return _conv(self.c2, h2, dt, res=sc, res_mode=L.VT_RES_ADD), (x, h1, c1, h2)
 
-    def backward(self, saved, dy, grads):
+    def lean(self, saved):
+        x, _h1, c1, _h2 = saved
+        return (x, None, c1, None)
+
+    def backward(self, saved, dy, grads, dt):
         x, h1, c1, h2 = saved
+        if h2 is None and _reads_input(self.c2):
+            h2 = _norm(self.blk.norm2, c1, True, dt)
         dh2 = _conv_backward(self.c2, h2, dy, grads)
+        del h2
         dc1 = _norm_backward(self.blk.norm2, c1, dh2, True, grads)
+        if h1 is None and _reads_input(self.c1):
+            h1 = _norm(self.blk.norm1, x, True, dt)
         dh1 = _conv_backward(self.c1, h1, dc1, grads)
+        del h1
         dx = _norm_backward(self.blk.norm1, x, dh1, True, grads)
         if self.nin is None:
             return ops.grad_add(dx, dy)
         return _conv_backward(self.nin, x, dy, grads, acc=dx)
 
 
-class _AttnStage:
+class _AttnStage(_Stage):
     """AttnBlockWrapper: LN, q / k / v 1x1x1, softmax(q k^T / sqrt(C)) v per frame, proj_out, + x"""
 
     def __init__(self, blk):
@@ -136,7 +172,10 @@ class _AttnStage:
         o = ops.gemm_nt(p, ops.transpose_batched(v, ld_out=Sp)).view(B, T, H, W, Cc)
         return _conv(self.proj, o, dt, res=x, res_mode=L.VT_RES_ADD), (x, hn, q, k, v, p, o)
 
-    def backward(self, saved, dy, grads):
+    def lean(self, saved):
+        return (saved[0], None) + tuple(saved[2:])
+
+    def backward(self, saved, dy, grads, dt):
         x, hn, q, k, v, p, o = saved
         B, T, H, W, Cc = x.shape
         Z, S = q.shape[:2]
@@ -147,13 +186,16 @@ class _AttnStage:
         ds = ops.softmax_rows_backward(p, dp, float(Cc) ** -0.5, cols=S, ld_out=Sp)
         dq = ops.gemm_nt(ds, ops.transpose_batched(k, ld_out=Sp))                                                # dQ = dS K
         dk = ops.gemm_nt(ops.transpose_batched(ds, cols=S, ld_out=Sp), ops.transpose_batched(q, ld_out=Sp))      # dK = dS^T Q
+        if hn is None and any(_reads_input(s) for s in (self.q, self.k, self.v)):
+            hn = _norm(self.blk.norm, x, False, dt)
         dhn = None
         for s, g in ((self.q, dq), (self.k, dk), (self.v, dv)):
             dhn = _conv_backward(s, hn, g.view(B, T, H, W, Cc), grads, acc=dhn)
+        del hn
         return ops.grad_add(_norm_backward(self.blk.norm, x, dhn, False, grads), dy)
 
 
-class _SpaceUpStage:
+class _SpaceUpStage(_Stage):
     """Upsample: nearest x2 + conv3x3 as ONE convolution whose gather folds the up-sampling (the view tests/backward_sites.py takes)"""
 
     def __init__(self, up):
@@ -165,11 +207,11 @@ class _SpaceUpStage:
     def forward(self, x, dt):
         return _conv(self.s, x, dt), (x,)
 
-    def backward(self, saved, dy, grads):
+    def backward(self, saved, dy, grads, dt):
         return _conv_backward(self.s, saved[0], dy, grads)
 
 
-class _TimeUpStage:
+class _TimeUpStage(_Stage):
     """TimeUpsampleResCausal2x on a whole clip: u = up(x) (nearest, or the v1.1 first-chunk trilinear head / tail split), y = a u + (1 - a) conv(u)"""
 
     def __init__(self, up):
@@ -194,7 +236,7 @@ class _TimeUpStage:
         c = _conv(self.s, u, dt)
         return ops.upsample_mix(u, c, self.up.mix_factor.detach(), ch=self.s.cout), (u, c, x.shape)
 
-    def backward(self, saved, dy, grads):
+    def backward(self, saved, dy, grads, dt):
         u, c, xshape = saved
         du, dc, dmix = ops.upsample_mix_backward(dy, u, c, self.up.mix_factor.detach(), ch=self.s.cout)
         grads[self.up.mix_factor] = dmix
@@ -229,8 +271,25 @@ def check_supported(dec):
         raise NotImplementedError(f"decode_with_grad: compute dtype {dec.compute_dtype}: the backward kernels take fp32 or bf16 (fp16 has no loss scaling here)")
 
 
-def train_forward(dec, z):
+class Tape(typing.NamedTuple):
+    """what train_forward leaves for train_backward"""
+    stages: list
+    saved: list                    # per stage: its saved tuple ("none"), the tuple without LayerNorm outputs ("norms"), its input ("stages")
+    cin: _Site
+    cout: _Site
+    h0: torch.Tensor               # the latent rows
+    h: torch.Tensor                # the tensor in front of norm_out
+    hn: typing.Optional[torch.Tensor]     # norm_out's output; None when the backward rebuilds it
+    trim: int
+    dt: torch.dtype
+    recompute: str
+    versions: typing.Optional[list]       # [(name, p._version)] of every decoder parameter at forward time; None for "none"
+    arith: typing.Optional[str]           # PackedCache.arith the forward packed its weights with
+
+
+def train_forward(dec, z, recompute="none"):
     """the recording pass: (x_hat NCTHW fp32, tape)"""
+    check_recompute(recompute)
     dt = dec.compute_dtype
     stages = [_stage(m) for m in dec.train_stage_modules()]
     cin, cout = _site(dec.conv_in), _site(dec.conv_out)
@@ -238,28 +297,102 @@ def train_forward(dec, z):
     h = _conv(cin, h0, dt)
     saved = []
     for st in stages:
+        if recompute == "stages":
+            saved.append(h)                         # the stage's input alone: the backward runs st.forward again
+            h = st.forward(h, dt)[0]
+            continue
         h, keep = st.forward(h, dt)
-        saved.append(keep)
+        saved.append(keep if recompute == "none" else st.lean(keep))
     hn = _norm(dec.norm_out, h, True, dt)
     trim = dec.time_padding if dec.version == "v1_0" else 0
     y = _conv(cout, hn, dt, out_layout=L.VT_NCTHW, t_trim=trim)
-    return y, (stages, saved, cin, cout, h0, h, hn, trim, dt)
+    if recompute == "none":
+        return y, Tape(stages, saved, cin, cout, h0, h, hn, trim, dt, recompute, None, None)
+    # what a recomputation must find unchanged: every parameter (the packed-weight caches repack on a new version) and the weight arithmetic
+    versions = [(n, p._version) for n, p in dec.named_parameters()]
+    return y, Tape(stages, saved, cin, cout, h0, h, None, trim, dt, recompute, versions, cin.pack.arith)
+
+
+def tape_tensors(tape):
+    """the distinct tensors a tape holds between forward and backward (tensors that share storage once)"""
+    seen, out = set(), []
+
+    def visit(v):
+        if isinstance(v, torch.Tensor):
+            key = v.untyped_storage().data_ptr() or id(v)          # empty tensors all report address 0: each is its own
+            if key not in seen:
+                seen.add(key)
+                out.append(v)
+        elif isinstance(v, (tuple, list)) and not isinstance(v, torch.Size):
+            for e in v:
+                visit(e)
+
+    visit(tape.saved)
+    visit((tape.h0, tape.h, tape.hn))
+    return out
+
+
+def tape_bytes(tape):
+    """bytes of activations a tape keeps alive: numel * element_size over tape_tensors(tape)"""
+    return sum(t.numel() * t.element_size() for t in tape_tensors(tape))
+
+
+def _check_unchanged(dec, versions):
+    for (name, ver), (_n, p) in zip(versions, dec.named_parameters()):
+        if p._version != ver:
+            raise RuntimeError(f"decode_with_grad: decoder parameter {name!r} was modified in place between the forward and this backward "
+                               f"(version {ver} -> {p._version}): the recomputation would run with the new weights. Call backward() before "
+                               f"optimizer.step(), or use recompute=\"none\"")
+
+
+class _tape_arith:
+    """the packed-weight arithmetic of the forward for the duration of a recomputing backward (set_compute_dtype may have moved on: a
+    forward is only accepted in fp32 / bf16, arith None, but "bf16x3" may be chosen before the backward runs).  packing.set_arith gives
+    every non-pinned cache under a module the same arithmetic, so conv_in's cache (`probe`) speaks for all of them, here and on exit"""
+
+    def __init__(self, dec, arith, probe):
+        self.dec, self.arith, self.was = dec, arith, probe.arith
+
+    def __enter__(self):
+        if self.was != self.arith:
+            packing.set_arith(self.dec, self.arith)
+
+    def __exit__(self, *exc):
+        if self.was != self.arith:
+            packing.set_arith(self.dec, self.was)
 
 
 def train_backward(dec, tape, cot, need_dz):
     """({parameter: gradient fp32 in the parameter's layout}, dz NCTHW fp32 or None) for the cotangent of train_forward's result"""
-    stages, saved, cin, cout, h0, h, hn, trim, dt = tape
+    *_, recompute, versions, arith = tape          # (a tape already used up is None: a second backward fails here, as it always has)
+    if recompute == "none":
+        return _backward(dec, tape, cot, need_dz)
+    _check_unchanged(dec, versions)
+    with _tape_arith(dec, arith, tape.cin.pack):
+        return _backward(dec, tape, cot, need_dz)
+
+
+def _backward(dec, tape, cot, need_dz):
+    stages, saved, cin, cout, h0, h, hn, trim, dt, recompute, _versions, _arith = tape
     grads = {}
     dy = ops.grad_ncthw_to_ndhwc(cot.contiguous().float(), dt, tpad=trim, ld=ops.pad_channels(cout.cout))
+    if hn is None and _reads_input(cout):
+        hn = _norm(dec.norm_out, h, True, dt)
     d = _conv_backward(cout, hn, dy, grads)
+    del hn
     if dt != torch.float32 and _wants(cout.conv.bias):
         # conv_out's bias gradient is the plain sum of the cotangent: taken from the fp32 cotangent, not from its 16-bit rounding (the sum of
         # ~10^6 rounding errors is 1e-3 of a sum that partly cancels) -- vt_conv_wgrad of a 1x1x1 site on the fp32 rows, its db alone
         dy32 = ops.grad_ncthw_to_ndhwc(cot.contiguous().float(), torch.float32, tpad=trim, ld=dy.shape[-1])
         grads[cout.conv.bias] = ops.conv_wgrad(dy32, dy32, ConvGeom(), cin=cout.cout, cout=cout.cout)[1]
     d = _norm_backward(dec.norm_out, h, d, True, grads)
-    for st, keep in zip(reversed(stages), reversed(saved)):
-        d = st.backward(keep, d, grads)
+    for i in reversed(range(len(stages))):
+        keep = saved[i]
+        if recompute == "stages":
+            keep = stages[i].forward(keep, dt)[1]           # the stage's saved tuple again, from its input; its output is dropped here
+        d = stages[i].backward(keep, d, grads, dt)
+        if recompute != "none":
+            saved[i] = keep = None                          # the tape is used up as the walk goes
     dz = _conv_backward(cin, h0, d, grads, need_dx=need_dz)
     return grads, (ops.ndhwc_to_ncthw(dz, cin.cin) if need_dz else None)
 
@@ -268,8 +401,8 @@ class DecodeFunction(torch.autograd.Function):
     """decoder.forward_train(z) as one autograd node: inputs (z, every decoder parameter), output x_hat"""
 
     @staticmethod
-    def forward(ctx, dec, z, *params):
-        y, tape = train_forward(dec, z)
+    def forward(ctx, dec, z, recompute, *params):
+        y, tape = train_forward(dec, z, recompute)
         ctx.dec, ctx.tape, ctx.params = dec, tape, params
         return y
 
@@ -280,15 +413,16 @@ class DecodeFunction(torch.autograd.Function):
         ctx.tape = None
         out = []
         for i, p in enumerate(ctx.params):
-            g = grads.get(p) if ctx.needs_input_grad[2 + i] else None
-            if ctx.needs_input_grad[2 + i] and g is None:
+            g = grads.get(p) if ctx.needs_input_grad[3 + i] else None
+            if ctx.needs_input_grad[3 + i] and g is None:
                 raise RuntimeError("decode_with_grad: a decoder parameter received no gradient")
             out.append(None if g is None else g.view(p.shape))
-        return (None, dz) + tuple(out)
+        return (None, dz, None) + tuple(out)
 
 
-def forward_train(dec, z):
+def forward_train(dec, z, recompute="none"):
+    check_recompute(recompute)
     check_supported(dec)
     if not (isinstance(z, torch.Tensor) and z.dim() == 5 and z.dtype == torch.float32):
         raise TypeError("decode_with_grad: z must be an fp32 [B, D, T', H', W'] tensor")
-    return DecodeFunction.apply(dec, z, *dec.parameters())
+    return DecodeFunction.apply(dec, z, recompute, *dec.parameters())

@@ -300,12 +300,19 @@ class AutoencodingEngine(nn.Module):
             z = self.indices_to_latent(z)
         return self._run_decoder(z)
 
-    def decode_with_grad(self, z: torch.Tensor) -> torch.Tensor:
+    def decode_with_grad(self, z: torch.Tensor, recompute: str = "none") -> torch.Tensor:
         """decode(z) as a differentiable call (decoder fine-tuning on a frozen encoder, the reference's `fix_encoder: true`): the same
         fp32 NCTHW tensor, attached to the autograd graph by one torch.autograd.Function whose backward runs on the HIP kernels and
         fills `.grad` of every `decoder.*` parameter that requires it, and of z (vidtok_amd/backward.py).  A whole clip, causal
         LayerNorm decoders, compute dtype fp32 or bf16 (set_compute_dtype or the caller's autocast); graphs do not apply to this path.
-        Raises NotImplementedError for everything else rather than returning gradients of something else."""
+        Raises NotImplementedError for everything else rather than returning gradients of something else.
+        `recompute` trades the activations kept for the backward against arithmetic, with the same bits in every result: "none" keeps
+        every convolution input and pre-norm row, "norms" rebuilds the LayerNorm outputs in the backward, "stages" keeps one tensor per
+        stage and re-runs each stage's forward in the backward.  The two rebuild with the weights as they are at backward time, so a
+        decoder parameter modified in place between this call and `.backward()` raises RuntimeError there."""
+        from .backward import check_recompute
+
+        check_recompute(recompute)
         self._sync_autocast(z)
         if self.use_tiling:
             raise NotImplementedError("decode_with_grad: temporal tiling / sessions have no backward (a whole clip only)")
@@ -313,7 +320,7 @@ class AutoencodingEngine(nn.Module):
             raise NotImplementedError(f"decode_with_grad: arithmetic {self.arith!r}: the backward kernels take fp32 or bf16 operands")
         if not hasattr(self.decoder, "forward_train"):
             raise NotImplementedError(f"decode_with_grad: {type(self.decoder).__name__} (the non-causal family) has no backward")
-        return self.decoder.forward_train(z)
+        return self.decoder.forward_train(z, recompute)
 
     @torch.no_grad()
     def forward(self, x: Any) -> Tuple[torch.Tensor, torch.Tensor, dict]:

@@ -848,13 +848,14 @@ class DecoderCausal3DPadding(nn.Module):
                     stages.append(self.up_temporal[i_level].upsample)
         return stages
 
-    def forward_train(self, z):
+    def forward_train(self, z, recompute="none"):
         """forward(z) attached to the autograd graph: `.backward()` fills `.grad` of every decoder parameter that requires it and of
         z (vidtok_amd/backward.py: a recording pass of un-fused launches + the HIP backward kernels).  A whole clip, LayerNorm
-        decoders, compute dtype fp32 or bf16; everything else raises NotImplementedError."""
+        decoders, compute dtype fp32 or bf16; everything else raises NotImplementedError.  `recompute`: "none" | "norms" | "stages",
+        how much of the recording the backward rebuilds instead of keeping (same bits either way)."""
         from . import backward
 
-        return backward.forward_train(self, z)
+        return backward.forward_train(self, z, recompute)
 
     @torch.no_grad()
     def forward(self, z):

@@ -9,7 +9,7 @@ call, back-propagates a seeded cotangent, and returns what each convolution and 
             behind the SiLU where there is one), dy_pre (gradient reaching y_pre THROUGH the norm only), gamma.grad, beta.grad
 
 `kernel_conv_operands` / `kernel_norm_operands` turn a site into what the engine would hand the kernel: the geometry and time-pad
-mode come from the engine's own modules (`CausalConv3d.geom`, `CausalConv1d`, `_G3x3`, `_G1x1`, `_tmode_and_cache`), activations go
+mode come from the engine's own conv-site objects (`packing.ConvSite`: `.geom`, `.clip_tmode`), activations go
 NCTHW -> NDHWC with `ops.pad_channels` stored channels whose pad lanes carry garbage.  The per-site fp64 references (`ref_wgrad`,
 `ref_wgrad_taps`, `ref_ln`) are computed from exactly those operands.
 """
@@ -191,30 +191,27 @@ def compared_parameters(conv_sites, norm_sites):
 
 # ---- site -> kernel operands ----------------------------------------------------------------------------------------------
 def site_geometry(model, site: ConvSite):
-    """(ConvGeom, tmode, pre-up-sample NCTHW input) the engine's modules give for this site on the first chunk of a clip"""
-    from vidtok_amd import lib as L
+    """(ConvGeom, tmode, pre-up-sample NCTHW input) the engine's own site object gives for this convolution on a whole clip"""
     from vidtok_amd import modules as M
 
-    mod = model.get_submodule(site.name)
     owner = model.get_submodule(site.name.rsplit(".", 1)[0])
     x = site.x_in
-    if isinstance(owner, M.CausalConv3d) or isinstance(owner, M.CausalConv1d):
+    if isinstance(owner, M.Upsample):             # nearest x2 in space, folded into the gather of the training path's one launch
+        s = owner.fold_site
+        assert s.geom.ups_s == 1 and torch.equal(x[..., 0::2, 0::2], x[..., 1::2, 1::2])       # the folded up-sampling really is a repetition
+        return s.geom, s.clip_tmode, x[..., 0::2, 0::2]
+    if hasattr(owner, "_tmode_and_cache"):        # a causal convolution: the owner holds the chunk state
+        s = owner.site
         tmode, cache = owner._tmode_and_cache(owner.version, owner.time_pad)
-        assert cache is None                      # a whole clip: no chunk-to-chunk cache form
-        if isinstance(owner, M.CausalConv1d):
-            return M.ConvGeom(kt=owner.k, st=owner.stride, pt=owner.time_pad), tmode, x
+        assert cache is None and tmode == s.clip_tmode                                           # a whole clip: no chunk-to-chunk cache form
         up = model.get_submodule(site.name.rsplit(".", 2)[0])
         if isinstance(up, M.TimeUpsampleResCausal2x) and not (up.version == "v1_1" and up.enable_cached):
             # nearest x2 in time, folded into the gather: the kernel reads the tensor in front of the up-sampling
             assert torch.equal(x[:, :, 0::2], x[:, :, 1::2])
-            return owner.geom(1), tmode, x[:, :, 0::2]
-        return owner.geom(0), tmode, x            # (v1.1 trilinear: the interpolated tensor as it was convolved)
-    assert isinstance(mod, torch.nn.Conv2d), (site.name, type(mod))
-    if isinstance(owner, M.Upsample):             # nearest x2 in space, folded into the gather
-        assert torch.equal(x[..., 0::2, 0::2], x[..., 1::2, 1::2])
-        return dataclasses.replace(M._G3x3, ups_s=1), L.VT_TPAD_ZERO, x[..., 0::2, 0::2]
-    g = {(3, 3): M._G3x3, (1, 1): M._G1x1}[tuple(mod.kernel_size)]
-    return g, L.VT_TPAD_ZERO, x
+            return dataclasses.replace(s.geom, ups_t=1), tmode, x[:, :, 0::2]
+        return s.geom, tmode, x                   # (v1.1 trilinear: the interpolated tensor as it was convolved)
+    s = next(s for s in owner.sites if s is not None and s.conv is model.get_submodule(site.name))
+    return s.geom, s.clip_tmode, x
 
 
 def to_ndhwc(t, ld, dtype, seed):

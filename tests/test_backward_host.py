@@ -144,7 +144,7 @@ def test_edge_geometries_are_the_engines_own():
     c1 = M.CausalConv1d(8, 8, 3, stride=2)
     assert G["time-down 3x1x1 st2"] == M.ConvGeom(kt=c1.k, st=c1.stride, pt=c1.time_pad)
     assert G["1x3x3"] == M._G3x3 and G["1x1x1"] == M._G1x1
-    assert {G[f"phase 2x2 {py}{px}"] for py in (0, 1) for px in (0, 1)} == {g for _py, _px, _pack, g in M.Upsample(8, True)._parity}
+    assert {G[f"phase 2x2 {py}{px}"] for py in (0, 1) for px in (0, 1)} == {site.geom for _py, _px, site in M.Upsample(8, True).parity_sites}
 
 
 def test_tap_by_tap_wgrad_reference_matches_autograd():

@@ -258,7 +258,7 @@ def test_backward_rebuilds_in_the_tapes_arithmetic(mode):
             got = step(model, mode, between=lambda: model.set_compute_dtype(then))[0]
             assert model.decoder.compute_dtype == torch.float32 and model.arith == ("fp32" if then == torch.float32 else "bf16x3")
             assert_same_bits(got, reference_in(first))
-        assert model.decoder.conv_in._pack.arith == "bf16x3"      # and the mode the caller chose is back in force afterwards
+        assert model.decoder.conv_in.site.pack.arith == "bf16x3"      # and the mode the caller chose is back in force afterwards
     finally:
         model.set_compute_dtype(torch.float32)
 

@@ -95,7 +95,7 @@ def test_split_bf16_weight_planes_and_mode_plumbing(emulated_ops):
     """"bf16x3": pack_split3's plane layout ([hi 16 | lo 16] bf16 per 16 k, K padded to 32, hi + lo within 2^-16 of w), and
     set_compute_dtype("bf16x3") reaching every convolution's PackedCache (not the attention's W_v row operand) with fp32
     storage -- the host graph in that mode stays within the fp32 tolerance of the oracle; switching back restores fp32 rows"""
-    from vidtok_amd.packing import PackedCache, pack_split3
+    from vidtok_amd.packing import pack_split3, packed_caches
 
     w = torch.randn(5, 40)
     p = pack_split3(w)
@@ -110,7 +110,7 @@ def test_split_bf16_weight_planes_and_mode_plumbing(emulated_ops):
                         ("vidtok_v1_1/vidtok_kl_causal_488_16chn_v1_1", (1, 3, 9, 32, 32))):
         model, cfg, sd = build_model(name, seed=3, dtype="bf16x3")
         assert model.arith == "bf16x3" and model.encoder.compute_dtype == torch.float32
-        caches = [v for m in model.modules() for v in m.__dict__.values() if isinstance(v, PackedCache)]
+        caches = list(packed_caches(model))
         assert caches and all((c.arith == "bf16x3") != c.pin_native for c in caches) and any(c.pin_native for c in caches)
         ora = build_oracle(cfg, sd)
         x = torch.rand(*shape) * 2 - 1
@@ -127,6 +127,46 @@ def test_split_bf16_weight_planes_and_mode_plumbing(emulated_ops):
         torch.manual_seed(1)
         z3, dec3, _ = model(x)
         assert rel_err(dec3, dec2) < 5e-5
+
+
+def test_set_arith_reaches_every_packed_cache_of_a_model():
+    """packing.set_arith against an enumeration that does not use its rule: every PackedCache the garbage collector knows and that can
+    be reached from the model by following references (through containers and instances; not into classes, modules, functions or
+    tensors, which lead to the rest of the process) -- after a forward and, for the causal families, a decode_with_grad + backward,
+    so that whatever is made on first use exists.  Non-pinned caches follow the mode both ways, pinned ones (W_v as a GEMM row
+    operand) never."""
+    import gc
+    import types
+
+    from torch_backward_ref import patched_ops
+    from vidtok_amd import packing
+
+    def reachable_caches(model):
+        seen, todo = set(), [model]
+        while todo:
+            o = todo.pop()
+            if id(o) in seen or isinstance(o, (type, types.ModuleType, types.FunctionType, types.BuiltinFunctionType, types.MethodType,
+                                               torch.Tensor, str, bytes, int, float)):
+                continue
+            seen.add(id(o))
+            todo.extend(gc.get_referents(o))
+        return [o for o in gc.get_objects() if isinstance(o, packing.PackedCache) and id(o) in seen]
+
+    for name, shape, causal in (("vidtok_v1_1/vidtok_kl_causal_488_4chn_v1_1", (1, 3, 5, 16, 16), True),
+                                ("vidtok_kl_causal_488_4chn", (1, 3, 5, 16, 16), True),
+                                ("vidtok_kl_noncausal_488_4chn", (1, 3, 4, 16, 16), False)):
+        model, _cfg, _sd = build_model(name, seed=3)
+        with patched_ops():
+            z = model(torch.rand(*shape) * 2 - 1)[0]
+            if causal:
+                model.decode_with_grad(z.clone().requires_grad_(True)).sum().backward()
+        caches = reachable_caches(model)
+        n_convs = sum(isinstance(m, (torch.nn.Conv1d, torch.nn.Conv2d, torch.nn.Conv3d)) for m in model.modules())
+        assert len(caches) > n_convs and any(c.pin_native for c in caches) and any(c._entries for c in caches)
+        for arith in (packing.ARITH_SPLIT3, None):
+            packing.set_arith(model, arith)
+            wrong = [c for c in caches if c.arith != (None if c.pin_native else arith)]
+            assert not wrong, (name, arith, len(wrong), len(caches))
 
 
 @pytest.mark.parametrize("name,shape", [
@@ -334,6 +374,11 @@ def test_graph_cache_bookkeeping_and_engine_copies():
         assert other._genc.fn.__self__ is other and other._gdec.fn.__self__ is other
         assert other._genc.state_get.__self__ is other and other._genc.fn.__func__ is type(model)._encoder_fn
         assert torch.equal(other.state_dict()["encoder.conv_in.conv.weight"], model.state_dict()["encoder.conv_in.conv.weight"])
+        # a copied conv site points at the COPY's parameter holder (packing.ConvSite is a plain object next to it)
+        up, blk = other.decoder.up[1].upsample, other.decoder.up[1].block[0]
+        assert other.decoder.conv_in.site.conv is other.decoder.conv_in.conv and blk.sites[0].conv is blk.conv1
+        assert up.fold_site.conv is up.conv and all(s.conv is up.conv for _py, _px, s in up.parity_sites)
+        assert list(other.state_dict()) == list(model.state_dict())
 
 
 def test_autocast_region_switches_the_arithmetic_mode():

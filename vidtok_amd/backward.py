@@ -25,7 +25,6 @@ decoder parameter changed in place between forward and backward would be repacke
 A whole clip only (first-chunk form: zero pad for v1.0, first-frame replicate for v1.1; the chunk caches are neither read nor
 written), `norm_type: layernorm`, compute dtype fp32 or bf16.
 """
-import dataclasses
 import typing
 
 import torch
@@ -35,7 +34,7 @@ from . import modules as M
 from . import ops
 from .ops import ConvGeom
 from . import packing
-from .packing import DgradPackCache, PackedCache
+from .packing import ConvSite
 
 RECOMPUTE_MODES = ("none", "norms", "stages")
 
@@ -45,53 +44,25 @@ def check_recompute(recompute):
         raise ValueError(f"decode_with_grad: recompute={recompute!r}: one of {RECOMPUTE_MODES}")
 
 
-@dataclasses.dataclass
-class _Site:
-    """one convolution of the decoder as the kernels see it"""
-    conv: torch.nn.Module          # nn.Conv1d / Conv2d / Conv3d parameter holder
-    pack: PackedCache
-    geom: ConvGeom
-    tmode: int
-    cin: int
-    cout: int
-
-    def dpack(self):
-        return self.conv.__dict__.setdefault("_dgrad_pack", DgradPackCache())
-
-
-def _site(mod, pack=None, geom=None):
-    if isinstance(mod, (M.CausalConv3d, M.CausalConv1d)):
-        tmode = L.VT_TPAD_ZERO if (mod.version == "v1_0" or mod.time_pad == 0) else L.VT_TPAD_REPLICATE
-        g = mod.geom(0) if isinstance(mod, M.CausalConv3d) else ConvGeom(kt=mod.k, st=mod.stride, pt=mod.time_pad)
-        return _Site(mod.conv, mod._pack, g, tmode, mod.conv.in_channels, mod.chan_out)
-    return _Site(mod, pack, geom, L.VT_TPAD_ZERO, mod.in_channels, mod.out_channels)
-
-
-def _conv(s: _Site, x, dt, **kw):
-    w, b = s.pack.get(s.conv.weight, s.conv.bias, dt, cin_stored=x.shape[-1])
-    return ops.conv(x, w, b, s.geom, cout=s.cout, tmode=s.tmode, **kw)
-
-
 def _wants(p):
     return p is not None and p.requires_grad
 
 
-def _reads_input(s: _Site):
+def _reads_input(s: ConvSite):
     """does the backward of this convolution read its input (vt_conv_wgrad does; vt_conv_dgrad reads the weight only)"""
     return _wants(s.conv.weight) or _wants(s.conv.bias)
 
 
-def _conv_backward(s: _Site, x, dy, grads, acc=None, need_dx=True):
+def _conv_backward(s: ConvSite, x, dy, grads, acc=None, need_dx=True):
     """parameter gradients of one convolution into `grads`; returns dx (+ acc), or None when nobody asks for it"""
     if _reads_input(s):
-        dw, db = ops.conv_wgrad(x, dy, s.geom, cin=s.cin, cout=s.cout, tmode=s.tmode, bias=s.conv.bias is not None)
+        dw, db = ops.conv_wgrad(x, dy, s.geom, cin=s.cin, cout=s.cout, tmode=s.clip_tmode, bias=s.conv.bias is not None)
         grads[s.conv.weight] = dw.view(s.conv.weight.shape)
         if s.conv.bias is not None:
             grads[s.conv.bias] = db
     if not need_dx:
         return None
-    wt = s.dpack().get(s.conv.weight, dy.dtype, dy.shape[-1])
-    return ops.conv_dgrad(dy, wt, s.geom, cin=s.cin, cout=s.cout, tmode=s.tmode, acc=acc)
+    return ops.conv_dgrad(dy, s.dgrad_rows(dy.dtype, dy.shape[-1]), s.geom, cin=s.cin, cout=s.cout, tmode=s.clip_tmode, acc=acc)
 
 
 def _norm(norm, x, silu, dt):
@@ -118,19 +89,14 @@ class _ResStage(_Stage):
 
     def __init__(self, blk):
         self.blk = blk
-        if isinstance(blk, M.ResnetBlock):
-            self.c1, self.c2 = _site(blk.conv1, blk._p1, M._G3x3), _site(blk.conv2, blk._p2, M._G3x3)
-            self.nin = _site(blk.nin_shortcut, blk._p3, M._G1x1) if blk.in_channels != blk.out_channels else None
-        else:
-            self.c1, self.c2 = _site(blk.conv1), _site(blk.conv2)
-            self.nin = _site(blk.nin_shortcut) if blk.in_channels != blk.out_channels else None
+        self.c1, self.c2, self.nin = blk.sites
 
     def forward(self, x, dt):
         h1 = _norm(self.blk.norm1, x, True, dt)
-        c1 = _conv(self.c1, h1, dt)
+        c1 = self.c1.run_clip(h1, dt)
         h2 = _norm(self.blk.norm2, c1, True, dt)
-        sc = x if self.nin is None else _conv(self.nin, x, dt)
-        return _conv(self.c2, h2, dt, res=sc, res_mode=L.VT_RES_ADD), (x, h1, c1, h2)
+        sc = x if self.nin is None else self.nin.run_clip(x, dt)
+        return self.c2.run_clip(h2, dt, res=sc, res_mode=L.VT_RES_ADD), (x, h1, c1, h2)
 
     def lean(self, saved):
         x, _h1, c1, _h2 = saved
@@ -158,7 +124,7 @@ class _AttnStage(_Stage):
 
     def __init__(self, blk):
         self.blk = blk
-        self.q, self.k, self.v, self.proj = _site(blk.q), _site(blk.k), _site(blk.v), _site(blk.proj_out)
+        self.q, self.k, self.v, self.proj = blk.q.site, blk.k.site, blk.v.site, blk.proj_out.site
 
     def forward(self, x, dt):
         B, T, H, W, Cc = x.shape
@@ -166,11 +132,11 @@ class _AttnStage(_Stage):
         S, Z = H * W, B * T
         Sp = ops.pad_channels(S)
         hn = _norm(self.blk.norm, x, False, dt)
-        q, k, v = (_conv(s, hn, dt).view(Z, S, Cc) for s in (self.q, self.k, self.v))
+        q, k, v = (s.run_clip(hn, dt).view(Z, S, Cc) for s in (self.q, self.k, self.v))
         s = ops.gemm_nt(q, k, out_dtype=torch.float32)                               # [Z, S, S]
         p = ops.softmax_rows(s, float(Cc) ** -0.5, dt, ld_out=Sp)                     # [Z, S, Sp]
         o = ops.gemm_nt(p, ops.transpose_batched(v, ld_out=Sp)).view(B, T, H, W, Cc)
-        return _conv(self.proj, o, dt, res=x, res_mode=L.VT_RES_ADD), (x, hn, q, k, v, p, o)
+        return self.proj.run_clip(o, dt, res=x, res_mode=L.VT_RES_ADD), (x, hn, q, k, v, p, o)
 
     def lean(self, saved):
         return (saved[0], None) + tuple(saved[2:])
@@ -201,11 +167,10 @@ class _SpaceUpStage(_Stage):
     def __init__(self, up):
         if not up.with_conv:
             raise NotImplementedError("decode_with_grad: Upsample(with_conv=False) has no backward here")
-        pack = up.__dict__.setdefault("_train_pack", PackedCache())
-        self.s = _site(up.conv, pack, dataclasses.replace(M._G3x3, ups_s=1))
+        self.s = up.fold_site
 
     def forward(self, x, dt):
-        return _conv(self.s, x, dt), (x,)
+        return self.s.run_clip(x, dt), (x,)
 
     def backward(self, saved, dy, grads, dt):
         return _conv_backward(self.s, saved[0], dy, grads)
@@ -216,7 +181,7 @@ class _TimeUpStage(_Stage):
 
     def __init__(self, up):
         self.up = up
-        self.s = _site(up.conv)
+        self.s = up.conv.site
         self.trilinear = up.version == "v1_1" and up.enable_cached
 
     def _spans(self, T):
@@ -233,7 +198,7 @@ class _TimeUpStage(_Stage):
                 ops.time_lerp2x(ops.gather_frames(x, list(range(t0, t0 + n))), out=u, out_t0=2 * t0)
         else:
             u = ops.gather_frames(x, [t // 2 for t in range(2 * T)])
-        c = _conv(self.s, u, dt)
+        c = self.s.run_clip(u, dt)
         return ops.upsample_mix(u, c, self.up.mix_factor.detach(), ch=self.s.cout), (u, c, x.shape)
 
     def backward(self, saved, dy, grads, dt):
@@ -275,8 +240,8 @@ class Tape(typing.NamedTuple):
     """what train_forward leaves for train_backward"""
     stages: list
     saved: list                    # per stage: its saved tuple ("none"), the tuple without LayerNorm outputs ("norms"), its input ("stages")
-    cin: _Site
-    cout: _Site
+    cin: ConvSite
+    cout: ConvSite
     h0: torch.Tensor               # the latent rows
     h: torch.Tensor                # the tensor in front of norm_out
     hn: typing.Optional[torch.Tensor]     # norm_out's output; None when the backward rebuilds it
@@ -292,9 +257,9 @@ def train_forward(dec, z, recompute="none"):
     check_recompute(recompute)
     dt = dec.compute_dtype
     stages = [_stage(m) for m in dec.train_stage_modules()]
-    cin, cout = _site(dec.conv_in), _site(dec.conv_out)
+    cin, cout = dec.conv_in.site, dec.conv_out.site
     h0 = ops.ncthw_to_ndhwc(z.detach().contiguous().float(), dt)
-    h = _conv(cin, h0, dt)
+    h = cin.run_clip(h0, dt)
     saved = []
     for st in stages:
         if recompute == "stages":
@@ -305,7 +270,7 @@ def train_forward(dec, z, recompute="none"):
         saved.append(keep if recompute == "none" else st.lean(keep))
     hn = _norm(dec.norm_out, h, True, dt)
     trim = dec.time_padding if dec.version == "v1_0" else 0
-    y = _conv(cout, hn, dt, out_layout=L.VT_NCTHW, t_trim=trim)
+    y = cout.run_clip(hn, dt, out_layout=L.VT_NCTHW, t_trim=trim)
     if recompute == "none":
         return y, Tape(stages, saved, cin, cout, h0, h, hn, trim, dt, recompute, None, None)
     # what a recomputation must find unchanged: every parameter (the packed-weight caches repack on a new version) and the weight arithmetic

@@ -189,10 +189,11 @@ class AutoencodingEngine(nn.Module):
     def _params_version(self, which):
         """fingerprint of a sub-tree's parameters for the graph cache (graphs.py `version_fn`): the sum of their in-place
         version counters, which only grow.  The parameter lists are collected once and dropped by invalidate_graphs."""
-        cache = self.__dict__.setdefault("_graph_params", {})
-        ps = cache.get(which)
+        if "_graph_params" not in self.__dict__:
+            self._graph_params = {}
+        ps = self._graph_params.get(which)
         if ps is None:
-            ps = cache[which] = list(getattr(self, which).parameters())
+            ps = self._graph_params[which] = list(getattr(self, which).parameters())
         return sum(p._version for p in ps)
 
     def _encoder_version(self):

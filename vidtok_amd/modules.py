@@ -14,6 +14,7 @@ decoder drops 3 frames; "v1_1" = first-frame-replicate / cached causal padding, 
 up-sampling, chunk-to-chunk caches (`causal_cache`, `is_first_chunk`, `cache_offset` attributes
 exactly as model_3dcausal_v1_1.py:155-157,212-214 so an engine can drive them).
 """
+import dataclasses
 import functools
 import os
 
@@ -23,7 +24,7 @@ import torch.nn as nn
 from . import lib as L
 from . import ops
 from .ops import ConvGeom
-from .packing import (PackedCache, space_upsample_parity_mix, space_upsample_parity_weights, time_upsample_parity_mix,
+from .packing import (ConvSite, space_upsample_parity_mix, space_upsample_parity_weights, time_upsample_parity_mix,
                       time_upsample_parity_weights)
 
 
@@ -143,6 +144,18 @@ class _CausalState:
         self.causal_cache = None
         self.cache_offset = 0
 
+    def _clip_tmode(self):
+        """the time-pad mode on a whole clip (= the first chunk)"""
+        return L.VT_TPAD_ZERO if (self.version == "v1_0" or self.time_pad == 0) else L.VT_TPAD_REPLICATE
+
+    def run(self, x, dt, **kw):
+        """the launch of `self.site` in the time-pad mode of this chunk, then the chunk state for the next one"""
+        tmode, cache = self._tmode_and_cache(self.version, self.time_pad)
+        y = self.site.run(x, dt, tmode=tmode, cache=cache, **kw)
+        if self.version == "v1_1":
+            self._update_cache(x, self.time_pad)
+        return y
+
     def _tmode_and_cache(self, version, time_pad):
         if version == "v1_0" or time_pad == 0:
             return L.VT_TPAD_ZERO, None
@@ -157,7 +170,9 @@ class _CausalState:
         a chunk of a given kind reads and writes the same addresses every time, which is what lets a captured chunk
         (vidtok_amd/graphs.py) be replayed.  `causal_cache` (the reference's attribute, reset to None between clips) is
         bound to the buffer after each update; `_cache_bufs` survives the reset."""
-        bufs = self.__dict__.setdefault("_cache_bufs", {})
+        if "_cache_bufs" not in self.__dict__:
+            self._cache_bufs = {}
+        bufs = self._cache_bufs
         key = (tuple(shape), like.dtype, like.device)
         buf = bufs.get(key)
         if buf is None:
@@ -206,7 +221,7 @@ class CausalConv3d(nn.Module, _CausalState):
         self.time_pad = (ks[0] - 1) + (1 - st[0])
         self.chan_out = chan_out
         self.version = version
-        self._pack = PackedCache()
+        self.site = ConvSite(self.conv, self.geom(), clip_tmode=self._clip_tmode())
         self._init_state()
 
     def geom(self, ups_t=0):
@@ -215,14 +230,6 @@ class CausalConv3d(nn.Module, _CausalState):
         return ConvGeom(kt=kt, kh=kh, kw=kw, st=self.strides[0], sh=self.strides[1], sw=self.strides[2],
                         pt=self.time_pad, ph=hp // 2, pw=wp // 2, ph_hi=hp - hp // 2, pw_hi=wp - wp // 2,
                         ups_t=ups_t)
-
-    def run(self, x, dt, *, ups_t=0, **kw):
-        w, b = self._pack.get(self.conv.weight, self.conv.bias, dt, cin_stored=x.shape[-1])
-        tmode, cache = self._tmode_and_cache(self.version, self.time_pad)
-        y = ops.conv(x, w, b, self.geom(ups_t), cout=self.chan_out, tmode=tmode, cache=cache, **kw)
-        if self.version == "v1_1":
-            self._update_cache(x, self.time_pad)
-        return y
 
 
 class CausalConv1d(nn.Module, _CausalState):
@@ -235,26 +242,8 @@ class CausalConv1d(nn.Module, _CausalState):
         self.time_pad = (kernel_size - 1) + (1 - stride)
         self.chan_out = chan_out
         self.version = version
-        self._pack = PackedCache()
+        self.site = ConvSite(self.conv, ConvGeom(kt=self.k, st=self.stride, pt=self.time_pad), clip_tmode=self._clip_tmode())
         self._init_state()
-
-    def run(self, x, dt, **kw):
-        w, b = self._pack.get(self.conv.weight, self.conv.bias, dt, cin_stored=x.shape[-1])
-        tmode, cache = self._tmode_and_cache(self.version, self.time_pad)
-        g = ConvGeom(kt=self.k, st=self.stride, pt=self.time_pad)
-        y = ops.conv(x, w, b, g, cout=self.chan_out, tmode=tmode, cache=cache, **kw)
-        if self.version == "v1_1":
-            self._update_cache(x, self.time_pad)
-        return y
-
-
-class _Conv2dHolder:
-    """Runs an nn.Conv2d parameter set as a per-frame spatial conv on NDHWC."""
-
-    @staticmethod
-    def run(conv: nn.Conv2d, pack: PackedCache, x, dt, geom: ConvGeom, **kw):
-        w, b = pack.get(conv.weight, conv.bias, dt, cin_stored=x.shape[-1])
-        return ops.conv(x, w, b, geom, cout=conv.out_channels, **kw)
 
 
 _G3x3 = ConvGeom(kh=3, kw=3, ph=1, pw=1, ph_hi=1, pw_hi=1)
@@ -275,10 +264,12 @@ class Upsample(nn.Module):
         # up(x)[Y][X] = x[Y>>1][X>>1]: an output pixel of parity (py, px) sees a 2x2 window of x, so the 3x3 conv over
         # the up-sampled frame is four 2x2 convs over x with pre-summed taps (4/9 of the MACs), each writing its
         # parity class of the output: rows (a-1, a) for py = 0, (a, a+1) for py = 1, likewise for columns
-        self._parity = [(py, px, PackedCache(functools.partial(space_upsample_parity_weights, py=py, px=px),
-                                             mix=functools.partial(space_upsample_parity_mix, py=py, px=px)),
-                         ConvGeom(kh=2, kw=2, ph=1 - py, pw=1 - px, ph_hi=py, pw_hi=px))
-                        for py in (0, 1) for px in (0, 1)]
+        self.parity_sites = [(py, px, ConvSite(self.conv, ConvGeom(kh=2, kw=2, ph=1 - py, pw=1 - px, ph_hi=py, pw_hi=px),
+                                               transform=functools.partial(space_upsample_parity_weights, py=py, px=px),
+                                               mix=functools.partial(space_upsample_parity_mix, py=py, px=px)))
+                             for py in (0, 1) for px in (0, 1)]
+        # the whole 3x3 with the x2 folded into its gather: the one launch the training path differentiates (vidtok_amd/backward.py)
+        self.fold_site = ConvSite(self.conv, dataclasses.replace(_G3x3, ups_s=1))
 
     def run(self, x, dt, next_norm=None):
         x = plain(x)
@@ -293,9 +284,8 @@ class Upsample(nn.Module):
         cout = self.conv.out_channels
         ld = ops.pad_channels(cout)
         y = (torch.empty if ld == cout else torch.zeros)((B, T, 2 * H, 2 * W, ld), dtype=dt, device=x.device)
-        for py, px, pack, g in self._parity:
-            w, b = pack.get(self.conv.weight, self.conv.bias, dt, cin_stored=C)
-            ops.conv(x, w, b, g, cout=cout, out=y, out_s=(py, px))
+        for py, px, site in self.parity_sites:
+            site.run(x, dt, out=y, out_s=(py, px))
         return y
 
 
@@ -310,7 +300,7 @@ class Downsample(nn.Module):
         if not with_conv:       # avg_pool2d(2, 2) (model_3dcausal.py:228-229): no parameters
             return
         self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
-        self._pack = PackedCache()
+        self.site = ConvSite(self.conv, ConvGeom(kh=3, kw=3, sh=2, sw=2, ph=0, pw=0, ph_hi=1, pw_hi=1))
 
     def run(self, x, dt, next_norm=None):
         if not self.with_conv:
@@ -325,8 +315,7 @@ class Downsample(nn.Module):
             y = ops.conv(xp, self._pool_w[key], None, ConvGeom(kh=2, kw=2, sh=2, sw=2), cout=self.in_channels, ldy=C,
                          **_emit(next_norm))
             return _wrap(y, next_norm)
-        g = ConvGeom(kh=3, kw=3, sh=2, sw=2, ph=0, pw=0, ph_hi=1, pw_hi=1)
-        return _wrap(_Conv2dHolder.run(self.conv, self._pack, plain(x), dt, g, **_emit(next_norm)), next_norm)
+        return _wrap(self.site.run(plain(x), dt, **_emit(next_norm)), next_norm)
 
 
 class TimeDownsampleResCausal2x(nn.Module):
@@ -355,6 +344,37 @@ class TimeDownsampleResCausal2x(nn.Module):
                                    **_emit(next_norm)), next_norm)
 
 
+def time_parity_class(conv, geom, early):
+    """one parity class of a k=3 convolution over frame-repeated input, as a k=2 site over the same parameters (packing.time_upsample_parity_weights)"""
+    return ConvSite(conv, geom, transform=functools.partial(time_upsample_parity_weights, early=early),
+                    mix=functools.partial(time_upsample_parity_mix, early=early))
+
+
+def time_parity_upsample(sites, x, dt, mix_factor, next_norm):
+    """alpha * up(x) + (1 - alpha) * conv(up(x)) for up = every frame twice, as the two launches of `sites` (even frames, odd frames): each
+    writes its frames of the interleaved output; the mix operand up(x)[2j+p] is x[j]."""
+    B, T, H, W, _C = x.shape
+    cout = sites[0].cout
+    ld = ops.pad_channels(cout)
+    y = (torch.empty if ld == cout else torch.zeros)((B, 2 * T, H, W, ld), dtype=dt, device=x.device)
+    # the consumer's LayerNorm from the two launches' epilogues where they can take it (vt_conv_plan decides: bf16, Cout = 256
+    # on the 8-wave tile, option conv_tup_ln), else the consumer runs its own pass
+    emit = dict(_emit(next_norm))
+    n = None
+
+    def alloc_n():           # the LayerNorm twin, allocated by ops.conv only once vt_conv_plan says the launch emits it (pad lanes as y's)
+        return (torch.empty if ld == cout else torch.zeros)(y.shape, dtype=dt, device=x.device)
+
+    for par, site in enumerate(sites):
+        r = site.run(x, dt, res=x, res_mode=L.VT_RES_MIX, mix_factor=mix_factor, out=y, out_t=(2, par),
+                     **(dict(emit, ln_out=(alloc_n if n is None else n), ln_optional=True) if emit else {}))
+        if emit and not isinstance(r, tuple):
+            emit, n = {}, None
+        elif emit:
+            n = r[1]
+    return y if n is None else Normed(y, n, next_norm[0], next_norm[1])
+
+
 class TimeUpsampleResCausal2x(nn.Module):
     """alpha*up(x) + (1-alpha)*causal conv3d(up(x)); up = nearest (v1.0, folded into the conv's
     gather and into the mix operand's time index) or trilinear with a frame cache (v1.1)
@@ -371,8 +391,11 @@ class TimeUpsampleResCausal2x(nn.Module):
         self.version = version
         self.is_first_chunk = True
         self.causal_cache = None
-        self._parity_packs = (PackedCache(functools.partial(time_upsample_parity_weights, early=True), mix=functools.partial(time_upsample_parity_mix, early=True)),
-                              PackedCache(functools.partial(time_upsample_parity_weights, early=False), mix=functools.partial(time_upsample_parity_mix, early=False)))
+        # v1.0, up(x)[t] = x[t >> 1]: the 3 temporal taps of an output frame hit 2 input frames, so even / odd output frames are two
+        # k=2 causal convs over x with pre-summed weights (2/3 of the MACs of the 27-tap form):
+        #   o[2j] = (W0+W1) x[j-1] + W2 x[j]      o[2j+1] = W0 x[j-1] + (W1+W2) x[j]
+        g = ConvGeom(kt=2, kh=3, kw=3, pt=1, ph=1, pw=1, ph_hi=1, pw_hi=1)
+        self.parity_sites = (time_parity_class(self.conv.conv, g, early=True), time_parity_class(self.conv.conv, g, early=False))
 
     def _interp_v11(self, x):
         n, T = self.num_temp_upsample, x.shape[1]
@@ -408,33 +431,23 @@ class TimeUpsampleResCausal2x(nn.Module):
         x = plain(x)
         mf = self.mix_factor.detach()
         if self.version == "v1_0":
-            # up(x)[t] = x[t >> 1]: the 3 temporal taps of an output frame hit 2 input frames, so even / odd output
-            # frames are two k=2 causal convs over x with pre-summed weights (2/3 of the MACs of the 27-tap form):
-            #   o[2j] = (W0+W1) x[j-1] + W2 x[j]      o[2j+1] = W0 x[j-1] + (W1+W2) x[j]
-            # each launch writes its frames of the interleaved output; the mix operand up(x)[2j+p] is x[j].
-            B, T, H, W, C = x.shape
-            ld = ops.pad_channels(self.conv.chan_out)
-            y = (torch.empty if ld == self.conv.chan_out else torch.zeros)((B, 2 * T, H, W, ld), dtype=dt, device=x.device)
-            g = ConvGeom(kt=2, kh=3, kw=3, pt=1, ph=1, pw=1, ph_hi=1, pw_hi=1)
-            # the consumer's LayerNorm from the two launches' epilogues where they can take it (vt_conv_plan decides: bf16, Cout = 256
-            # on the 8-wave tile, option conv_tup_ln), else the consumer runs its own pass
-            emit = dict(_emit(next_norm))
-            n = None
-
-            def alloc_n():           # the LayerNorm twin, allocated by ops.conv only once vt_conv_plan says the launch emits it (pad lanes as y's)
-                return (torch.empty if ld == self.conv.chan_out else torch.zeros)(y.shape, dtype=dt, device=x.device)
-
-            for par, pack in enumerate(self._parity_packs):
-                w, b = pack.get(self.conv.conv.weight, self.conv.conv.bias, dt, cin_stored=C)
-                r = ops.conv(x, w, b, g, cout=self.conv.chan_out, tmode=L.VT_TPAD_ZERO, res=x, res_mode=L.VT_RES_MIX,
-                             mix_factor=mf, out=y, out_t=(2, par), **(dict(emit, ln_out=(alloc_n if n is None else n), ln_optional=True) if emit else {}))
-                if emit and not isinstance(r, tuple):
-                    emit, n = {}, None
-                elif emit:
-                    n = r[1]
-            return y if n is None else Normed(y, n, next_norm[0], next_norm[1])
+            return time_parity_upsample(self.parity_sites, x, dt, mf, next_norm)
         xi = self._interp_v11(x)
         return _wrap(self.conv.run(xi, dt, res=xi, res_mode=L.VT_RES_MIX, mix_factor=mf, **_emit(next_norm)), next_norm)
+
+
+def residual_block(blk, view, convs, x, dt, next_norm):
+    """LN-SiLU-conv LN-SiLU-conv (+ shortcut conv) + x, the body of every residual block of both families.  `view`: what the block's norms
+    see (GroupNorm statistics); `convs` = (conv1, conv2, shortcut or None), each answering run(x, dt, **kw): a ConvSite, or a causal
+    convolution, which adds the time-pad mode and cache of the chunk and keeps the next chunk's."""
+    conv1, conv2, nin = convs
+    h = blk.norm1.apply_ndhwc(x, True, dt, view)
+    x = plain(x)
+    # conv1's result is only ever seen through norm2 + SiLU: with LayerNorm the conv emits that directly
+    h = blk.norm2.after(lambda **kw: conv1.run(h, dt, **kw), True, dt, view)
+    if nin is not None:
+        x = nin.run(x, dt)
+    return _wrap(conv2.run(h, dt, res=x, res_mode=L.VT_RES_ADD, **_emit(next_norm)), next_norm)
 
 
 class ResnetBlock(nn.Module):
@@ -453,20 +466,19 @@ class ResnetBlock(nn.Module):
         self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1)
         if in_channels != out_channels:
             self.nin_shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, padding=0)
-        self._p1, self._p2, self._p3 = PackedCache(), PackedCache(), PackedCache()
+        self.sites = (ConvSite(self.conv1, _G3x3), ConvSite(self.conv2, _G3x3),
+                      ConvSite(self.nin_shortcut, _G1x1) if in_channels != out_channels else None)
 
-    def first_norm(self):
+    def first_norm(self, dt=None):
         return (self.norm1, True)
 
     def run(self, x, dt, next_norm=None):
-        h = self.norm1.apply_ndhwc(x, True, dt, SITE_FRAME)
-        x = plain(x)
-        # conv1's result is only ever seen through norm2 + SiLU: with LayerNorm the conv emits that directly
-        h = self.norm2.after(lambda **kw: _Conv2dHolder.run(self.conv1, self._p1, h, dt, _G3x3, **kw), True, dt, SITE_FRAME)
-        if self.in_channels != self.out_channels:
-            x = _Conv2dHolder.run(self.nin_shortcut, self._p3, x, dt, _G1x1)
-        return _wrap(_Conv2dHolder.run(self.conv2, self._p2, h, dt, _G3x3, res=x, res_mode=L.VT_RES_ADD,
-                                       **_emit(next_norm)), next_norm)
+        return residual_block(self, SITE_FRAME, self.sites, x, dt, next_norm)
+
+
+def _causal_convs(blk):
+    """(conv1, conv2, shortcut or None) of a block whose convolutions are causal ones"""
+    return blk.conv1, blk.conv2, (blk.nin_shortcut if blk.in_channels != blk.out_channels else None)
 
 
 class ResnetCausalBlock(nn.Module):
@@ -484,17 +496,13 @@ class ResnetCausalBlock(nn.Module):
         self.conv2 = CausalConv3d(out_channels, out_channels, 3, version=version)
         if in_channels != out_channels:
             self.nin_shortcut = CausalConv3d(in_channels, out_channels, 1, version=version)
+        self.sites = tuple(c and c.site for c in _causal_convs(self))         # as ResnetBlock.sites
 
-    def first_norm(self):
+    def first_norm(self, dt=None):
         return (self.norm1, True)
 
     def run(self, x, dt, next_norm=None):
-        h = self.norm1.apply_ndhwc(x, True, dt, SITE_FRAME)
-        x = plain(x)
-        h = self.norm2.after(lambda **kw: self.conv1.run(h, dt, **kw), True, dt, SITE_FRAME)
-        if self.in_channels != self.out_channels:
-            x = self.nin_shortcut.run(x, dt)
-        return _wrap(self.conv2.run(h, dt, res=x, res_mode=L.VT_RES_ADD, **_emit(next_norm)), next_norm)
+        return residual_block(self, SITE_FRAME, _causal_convs(self), x, dt, next_norm)
 
 
 class ResnetCausalBlock1D(nn.Module):
@@ -514,6 +522,7 @@ class ResnetCausalBlock1D(nn.Module):
         self.conv2 = CausalConv1d(out_channels, out_channels, 3, version=version)
         if in_channels != out_channels:
             self.nin_shortcut = CausalConv1d(in_channels, out_channels, 1, version=version)
+        self.sites = tuple(c and c.site for c in _causal_convs(self))
         if zero_init:
             self.conv2.conv.weight.data.zero_()
             self.conv2.conv.bias.data.zero_()
@@ -570,9 +579,7 @@ class ResnetCausalBlock1D(nn.Module):
         fusable = self._fusable(dt)
         tmode, caches, off = self._chunk_state(xp) if fusable else (L.VT_TPAD_ZERO, None, 0)
         if fusable and ops.temporal_block_supported(xp, tmode, self.in_channels, caches, off):
-            c = xp.shape[-1]
-            w1, b1 = self.conv1._pack.get(self.conv1.conv.weight, self.conv1.conv.bias, dt, cin_stored=c)
-            w2, b2 = self.conv2._pack.get(self.conv2.conv.weight, self.conv2.conv.bias, dt, cin_stored=c)
+            (w1, b1), (w2, b2) = (c.site.rows(dt, xp.shape[-1]) for c in (self.conv1, self.conv2))
             nxt = None
             if next_norm is not None and _EMIT_NEXT_NORM and next_norm[0].fusable and next_norm[0].norm.eps == self.norm1.norm.eps:
                 g, b = next_norm[0].affine()
@@ -582,12 +589,29 @@ class ResnetCausalBlock1D(nn.Module):
             if caches is not None:          # the launch has rewritten the chunk state in place
                 self.conv1.causal_cache, self.conv2.causal_cache = caches
             return out if nxt is None else Normed(out[0], out[1], next_norm[0], next_norm[1])
-        h = self.norm1.apply_ndhwc(x, True, dt, SITE_POS)
-        x = xp
-        h = self.norm2.after(lambda **kw: self.conv1.run(h, dt, **kw), True, dt, SITE_POS)
-        if self.in_channels != self.out_channels:
-            x = self.nin_shortcut.run(x, dt)
-        return _wrap(self.conv2.run(h, dt, res=x, res_mode=L.VT_RES_ADD, **_emit(next_norm)), next_norm)
+        return residual_block(self, SITE_POS, _causal_convs(self), x, dt, next_norm)
+
+
+def attention_block(blk, view, q, k, v_rows, proj_out, x, dt, next_norm):
+    """The body of both families' attention: q, k, proj_out answer run(x, dt, **kw) (a ConvSite or a causal convolution), `v_rows` is the
+    site whose packed rows are W_v."""
+    hn = blk.norm.apply_ndhwc(x, False, dt, view)
+    x = plain(x)
+    B, T, H, W, Cc = x.shape
+    S, Z = H * W, B * T
+    q = q.run(hn, dt).view(Z, S, Cc)
+    k = k.run(hn, dt).view(Z, S, Cc)
+    wv, bv = v_rows.rows(dt, Cc)
+    Sp = ops.pad_channels(S)        # K-contiguous operands need 16-byte rows: pad S with zero columns
+    vT = ops.gemm_nt(wv.view(1, Cc, Cc), hn.view(Z, S, Cc), ld_out=Sp)                     # [Z, C, Sp]
+    if ops.flash_attention_supported(q, vT):
+        # one launch, online softmax: no [Z, S, S] scores in memory (1 GiB per latent frame at 1024 x 1024 input)
+        o = ops.flash_attention(q, k, vT, bv, float(Cc) ** -0.5).view(B, T, H, W, Cc)
+    else:
+        s = ops.gemm_nt(q, k, out_dtype=torch.float32)                                     # [Z, S, S]
+        p = ops.softmax_rows(s, float(Cc) ** -0.5, dt, ld_out=Sp)                          # [Z, S, Sp]
+        o = ops.gemm_nt(p, vT, bias=bv).view(B, T, H, W, Cc)
+    return _wrap(proj_out.run(o, dt, res=x, res_mode=L.VT_RES_ADD, **_emit(next_norm)), next_norm)
 
 
 class AttnBlockWrapper(nn.Module):
@@ -604,38 +628,18 @@ class AttnBlockWrapper(nn.Module):
         self.k = CausalConv3d(in_channels, in_channels, 1, version=version)
         self.v = CausalConv3d(in_channels, in_channels, 1, version=version)
         self.proj_out = CausalConv3d(in_channels, in_channels, 1, version=version)
-        self._v_rows = PackedCache(pin_native=True)     # W_v as the ROW operand of a GEMM against activations: plain rows in every mode
+        self.v_rows = ConvSite(self.v.conv, _G1x1, pin_native=True)     # W_v as the ROW operand of a GEMM against activations: plain rows in every mode
 
-    def first_norm(self):
+    def first_norm(self, dt=None):
         return (self.norm, False)
 
     def run(self, x, dt, next_norm=None):
-        hn = self.norm.apply_ndhwc(x, False, dt, SITE_FRAME)
-        x = plain(x)
-        B, T, H, W, Cc = x.shape
-        S, Z = H * W, B * T
-        q = self.q.run(hn, dt).view(Z, S, Cc)
-        k = self.k.run(hn, dt).view(Z, S, Cc)
-        wv, bv = self._v_rows.get(self.v.conv.weight, self.v.conv.bias, dt, cin_stored=Cc)
-        Sp = ops.pad_channels(S)        # K-contiguous operands need 16-byte rows: pad S with zero columns
-        vT = ops.gemm_nt(wv.view(1, Cc, Cc), hn.view(Z, S, Cc), ld_out=Sp)                     # [Z, C, Sp]
-        if ops.flash_attention_supported(q, vT):
-            # one launch, online softmax: no [Z, S, S] scores in memory (1 GiB per latent frame at 1024 x 1024 input)
-            o = ops.flash_attention(q, k, vT, bv, float(Cc) ** -0.5).view(B, T, H, W, Cc)
-        else:
-            s = ops.gemm_nt(q, k, out_dtype=torch.float32)                                     # [Z, S, S]
-            p = ops.softmax_rows(s, float(Cc) ** -0.5, dt, ld_out=Sp)                          # [Z, S, Sp]
-            o = ops.gemm_nt(p, vT, bias=bv).view(B, T, H, W, Cc)
-        return _wrap(self.proj_out.run(o, dt, res=x, res_mode=L.VT_RES_ADD, **_emit(next_norm)), next_norm)
+        return attention_block(self, SITE_FRAME, self.q, self.k, self.v_rows, self.proj_out, x, dt, next_norm)
 
 
 def first_norm_of(stage, dt=None):
     """(LayerNorm, silu) a stage wants applied to its input by its producer, or None (resamplers, fused temporal blocks)"""
-    if not hasattr(stage, "first_norm"):
-        return None
-    if isinstance(stage, ResnetCausalBlock1D):
-        return stage.first_norm(dt)
-    return stage.first_norm()
+    return stage.first_norm(dt) if hasattr(stage, "first_norm") else None
 
 
 def run_stages(stages, h, dt, last_norm=None, first=None, switch=None):

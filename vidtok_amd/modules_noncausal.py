@@ -10,37 +10,26 @@ What differs from the causal family (vidtok_amd/modules.py):
   * the encoder pads nothing in front: T must be a multiple of the temporal compression factor.
 The spatial blocks (ResnetBlock, Upsample, Downsample) are the same classes as in the causal family.
 """
-import functools
-
 import torch
 import torch.nn as nn
 
 from . import lib as L
 from . import ops
-from .modules import (SITE_CLIP, SITE_PIXEL, Downsample, Normalize, Normed, ResnetBlock, Upsample, _check_norm, _emit,
-                      _level_module, _wrap, first_norm_of, plain, run_stages)
+from .modules import (SITE_CLIP, SITE_PIXEL, Downsample, Normalize, ResnetBlock, Upsample, _check_norm, _emit, _level_module, _wrap,
+                      attention_block, first_norm_of, plain, residual_block, run_stages, time_parity_class, time_parity_upsample)
 from .ops import ConvGeom
-from .packing import PackedCache, time_upsample_parity_mix, time_upsample_parity_weights
+from .packing import ConvSite
 
 
-class _Conv3dSym:
-    """Runs a plain nn.Conv3d / nn.Conv1d parameter set with `padding = k // 2` on NDHWC."""
-
-    @staticmethod
-    def geom(conv, ups_t=0):
-        if isinstance(conv, nn.Conv1d):
-            (kt,), (st,), (pt,) = conv.kernel_size, conv.stride, conv.padding
-            return ConvGeom(kt=kt, st=st, pt=pt, pt_hi=pt, ups_t=ups_t)
-        kt, kh, kw = conv.kernel_size
-        st, sh, sw = conv.stride
-        pt, ph, pw = conv.padding
-        return ConvGeom(kt=kt, kh=kh, kw=kw, st=st, sh=sh, sw=sw, pt=pt, ph=ph, pw=pw, pt_hi=pt, ph_hi=ph, pw_hi=pw,
-                        ups_t=ups_t)
-
-    @staticmethod
-    def run(conv, pack: PackedCache, x, dt, geom=None, **kw):
-        w, b = pack.get(conv.weight, conv.bias, dt, cin_stored=x.shape[-1])
-        return ops.conv(x, w, b, geom or _Conv3dSym.geom(conv), cout=conv.out_channels, **kw)
+def _centred(conv, **kw):
+    """the site of a plain nn.Conv3d / nn.Conv1d parameter set with `padding = k // 2` (zero on both sides) on NDHWC"""
+    if isinstance(conv, nn.Conv1d):
+        (kt,), (st,), (pt,) = conv.kernel_size, conv.stride, conv.padding
+        return ConvSite(conv, ConvGeom(kt=kt, st=st, pt=pt, pt_hi=pt), **kw)
+    kt, kh, kw_ = conv.kernel_size
+    st, sh, sw = conv.stride
+    pt, ph, pw = conv.padding
+    return ConvSite(conv, ConvGeom(kt=kt, kh=kh, kw=kw_, st=st, sh=sh, sw=sw, pt=pt, ph=ph, pw=pw, pt_hi=pt, ph_hi=ph, pw_hi=pw), **kw)
 
 
 class TimeDownsampleRes2x(nn.Module):
@@ -51,14 +40,13 @@ class TimeDownsampleRes2x(nn.Module):
         super().__init__()
         self.conv = nn.Conv3d(in_channels, out_channels, 3, stride=(2, 1, 1), padding=(0, 1, 1))
         self.mix_factor = nn.Parameter(torch.Tensor([mix_factor]))
-        self._pack = PackedCache()
+        self.site = ConvSite(self.conv, ConvGeom(kt=3, kh=3, kw=3, st=2, pt=0, pt_hi=1, ph=1, pw=1, ph_hi=1, pw_hi=1))
 
     def run(self, x, dt, next_norm=None):
         x = plain(x)
         x1 = ops.time_avgpool3s2(x, L.VT_TPAD_ZERO_BACK)
-        g = ConvGeom(kt=3, kh=3, kw=3, st=2, pt=0, pt_hi=1, ph=1, pw=1, ph_hi=1, pw_hi=1)
-        return _wrap(_Conv3dSym.run(self.conv, self._pack, x, dt, g, res=x1, res_mode=L.VT_RES_MIX,
-                                    mix_factor=self.mix_factor.detach(), **_emit(next_norm)), next_norm)
+        return _wrap(self.site.run(x, dt, res=x1, res_mode=L.VT_RES_MIX, mix_factor=self.mix_factor.detach(), **_emit(next_norm)),
+                     next_norm)
 
 
 class TimeUpsampleRes2x(nn.Module):
@@ -70,39 +58,18 @@ class TimeUpsampleRes2x(nn.Module):
         self.conv = nn.Conv3d(in_channels, out_channels, 3, padding=1)
         self.mix_factor = nn.Parameter(torch.Tensor([mix_factor]))
         # centred window over up(x)[t] = x[t >> 1]:  o[2j] = W0 x[j-1] + (W1+W2) x[j],  o[2j+1] = (W0+W1) x[j] + W2 x[j+1]
-        self._parity = ((PackedCache(functools.partial(time_upsample_parity_weights, early=False), mix=functools.partial(time_upsample_parity_mix, early=False)),
-                         ConvGeom(kt=2, kh=3, kw=3, pt=1, pt_hi=0, ph=1, pw=1, ph_hi=1, pw_hi=1)),
-                        (PackedCache(functools.partial(time_upsample_parity_weights, early=True), mix=functools.partial(time_upsample_parity_mix, early=True)),
-                         ConvGeom(kt=2, kh=3, kw=3, pt=0, pt_hi=1, ph=1, pw=1, ph_hi=1, pw_hi=1)))
+        # (two k=2 convs with pre-summed taps: 2/3 of the MACs)
+        self.parity_sites = (time_parity_class(self.conv, ConvGeom(kt=2, kh=3, kw=3, pt=1, pt_hi=0, ph=1, pw=1, ph_hi=1, pw_hi=1), early=False),
+                             time_parity_class(self.conv, ConvGeom(kt=2, kh=3, kw=3, pt=0, pt_hi=1, ph=1, pw=1, ph_hi=1, pw_hi=1), early=True))
 
     def run(self, x, dt, next_norm=None):
-        x = plain(x)
-        B, T, H, W, C = x.shape
-        cout = self.conv.out_channels
-        ld = ops.pad_channels(cout)
-        y = (torch.empty if ld == cout else torch.zeros)((B, 2 * T, H, W, ld), dtype=dt, device=x.device)
-        # the consumer's LayerNorm from the two launches' epilogues where they can take it (modules.TimeUpsampleResCausal2x.run)
-        emit = dict(_emit(next_norm))
-        n = None
-
-        def alloc_n():               # allocated by ops.conv only once vt_conv_plan says the launch emits the LayerNorm (pad lanes as y's)
-            return (torch.empty if ld == cout else torch.zeros)(y.shape, dtype=dt, device=x.device)
-
-        for par, (pack, g) in enumerate(self._parity):      # two k=2 convs with pre-summed taps: 2/3 of the MACs
-            w, b = pack.get(self.conv.weight, self.conv.bias, dt, cin_stored=C)
-            r = ops.conv(x, w, b, g, cout=cout, res=x, res_mode=L.VT_RES_MIX, mix_factor=self.mix_factor.detach(),
-                         out=y, out_t=(2, par), **(dict(emit, ln_out=(alloc_n if n is None else n), ln_optional=True) if emit else {}))
-            if emit and not isinstance(r, tuple):
-                emit, n = {}, None
-            elif emit:
-                n = r[1]
-        return y if n is None else Normed(y, n, next_norm[0], next_norm[1])
+        return time_parity_upsample(self.parity_sites, plain(x), dt, self.mix_factor.detach(), next_norm)
 
 
 class _ResnetSym(nn.Module):
     """LN-SiLU-conv-LN-SiLU-conv + x with centred convs; `make_conv(cin, cout, k)` builds the conv type."""
 
-    site = SITE_CLIP   # view the reference hands to this block's norms (GroupNorm statistics)
+    view = SITE_CLIP   # what the reference hands to this block's norms (GroupNorm statistics)
 
     def __init__(self, make_conv, *, in_channels, out_channels=None, conv_shortcut=False, dropout=0.0, temb_channels=0,
                  zero_init=False, use_checkpoint=False, norm_type="layernorm"):
@@ -121,24 +88,20 @@ class _ResnetSym(nn.Module):
         if zero_init:
             self.conv2.weight.data.zero_()
             self.conv2.bias.data.zero_()
-        self._p1, self._p2 = PackedCache(), PackedCache()
+        self.sites = (_centred(self.conv1), _centred(self.conv2), None)
 
-    def first_norm(self):
+    def first_norm(self, dt=None):
         return (self.norm1, True)
 
     def run(self, x, dt, next_norm=None):
-        h = self.norm1.apply_ndhwc(x, True, dt, self.site)
-        x = plain(x)
-        h = self.norm2.after(lambda **kw: _Conv3dSym.run(self.conv1, self._p1, h, dt, **kw), True, dt, self.site)
-        return _wrap(_Conv3dSym.run(self.conv2, self._p2, h, dt, res=x, res_mode=L.VT_RES_ADD, **_emit(next_norm)),
-                     next_norm)
+        return residual_block(self, self.view, self.sites, x, dt, next_norm)
 
 
 class ResnetBlock1D(_ResnetSym):
     """Temporal block on the "(b h w) c t" view of the reference = taps along T on NDHWC; conv2 zero-initialised
     (model_3dnoncausal.py:182-248)."""
 
-    site = SITE_PIXEL
+    view = SITE_PIXEL
 
     def __init__(self, **kw):
         super().__init__(lambda ci, co: nn.Conv1d(ci, co, kernel_size=3, stride=1, padding=1), **kw)
@@ -164,29 +127,14 @@ class AttnBlockWrapper(nn.Module):
         self.k = nn.Conv3d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
         self.v = nn.Conv3d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
         self.proj_out = nn.Conv3d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self._pq, self._pk, self._pv, self._po = PackedCache(), PackedCache(), PackedCache(pin_native=True), PackedCache()
+        # (q, k, W_v as a row operand: plain rows in every mode, proj_out)
+        self.sites = (_centred(self.q), _centred(self.k), _centred(self.v, pin_native=True), _centred(self.proj_out))
 
-    def first_norm(self):
+    def first_norm(self, dt=None):
         return (self.norm, False)
 
     def run(self, x, dt, next_norm=None):
-        hn = self.norm.apply_ndhwc(x, False, dt, SITE_CLIP)
-        x = plain(x)
-        B, T, H, W, Cc = x.shape
-        S, Z = H * W, B * T
-        q = _Conv3dSym.run(self.q, self._pq, hn, dt).view(Z, S, Cc)
-        k = _Conv3dSym.run(self.k, self._pk, hn, dt).view(Z, S, Cc)
-        wv, bv = self._pv.get(self.v.weight, self.v.bias, dt, cin_stored=Cc)
-        Sp = ops.pad_channels(S)
-        vT = ops.gemm_nt(wv.view(1, Cc, Cc), hn.view(Z, S, Cc), ld_out=Sp)
-        if ops.flash_attention_supported(q, vT):
-            o = ops.flash_attention(q, k, vT, bv, float(Cc) ** -0.5).view(B, T, H, W, Cc)
-        else:
-            s = ops.gemm_nt(q, k, out_dtype=torch.float32)
-            p = ops.softmax_rows(s, float(Cc) ** -0.5, dt, ld_out=Sp)
-            o = ops.gemm_nt(p, vT, bias=bv).view(B, T, H, W, Cc)
-        return _wrap(_Conv3dSym.run(self.proj_out, self._po, o, dt, res=x, res_mode=L.VT_RES_ADD, **_emit(next_norm)),
-                     next_norm)
+        return attention_block(self, SITE_CLIP, *self.sites, x, dt, next_norm)
 
 
 class Encoder3D(nn.Module):
@@ -233,7 +181,7 @@ class Encoder3D(nn.Module):
         self.mid.block_2 = ResnetNoncausalBlock(in_channels=block_in, out_channels=block_in, norm_type=norm_type)
         self.norm_out = Normalize(block_in, norm_type)
         self.conv_out = nn.Conv3d(block_in, self.out_channels, kernel_size=3, stride=1, padding=1)
-        self._pin, self._pout = PackedCache(), PackedCache()
+        self.site_in, self.site_out = _centred(self.conv_in), _centred(self.conv_out)
         if self.fix_encoder:
             for p in self.parameters():
                 p.requires_grad = False
@@ -255,10 +203,10 @@ class Encoder3D(nn.Module):
                     stages.append(self.down_temporal[i_level].downsample)
         stages += [self.mid.block_1, self.mid.attn_1, self.mid.block_2]
         first = first_norm_of(stages[0])
-        h = run_stages(stages, _Conv3dSym.run(self.conv_in, self._pin, h, dt, **_emit(first)), dt,
+        h = run_stages(stages, self.site_in.run(h, dt, **_emit(first)), dt,
                        last_norm=(self.norm_out, True), first=first)
         h = self.norm_out.apply_ndhwc(h, True, dt, SITE_CLIP)
-        return _Conv3dSym.run(self.conv_out, self._pout, h, dt, out_layout=L.VT_NCTHW)
+        return self.site_out.run(h, dt, out_layout=L.VT_NCTHW)
 
 
 class Decoder3D(nn.Module):
@@ -307,7 +255,7 @@ class Decoder3D(nn.Module):
             self.up_temporal.insert(0, up_t)
         self.norm_out = Normalize(block_in, norm_type)
         self.conv_out = nn.Conv3d(block_in, out_ch, kernel_size=3, stride=1, padding=1)
-        self._pin, self._pout = PackedCache(), PackedCache()
+        self.site_in, self.site_out = _centred(self.conv_in), _centred(self.conv_out)
         if self.fix_decoder:
             for p in self.parameters():
                 p.requires_grad = False
@@ -328,7 +276,7 @@ class Decoder3D(nn.Module):
                 if i_level in self.tempo_us:
                     stages.append(self.up_temporal[i_level].upsample)
         first = first_norm_of(stages[0])
-        h = run_stages(stages, _Conv3dSym.run(self.conv_in, self._pin, h, dt, **_emit(first)), dt,
+        h = run_stages(stages, self.site_in.run(h, dt, **_emit(first)), dt,
                        last_norm=(self.norm_out, True), first=first)
         h = self.norm_out.apply_ndhwc(h, True, dt, SITE_CLIP)
-        return _Conv3dSym.run(self.conv_out, self._pout, h, dt, out_layout=L.VT_NCTHW)
+        return self.site_out.run(h, dt, out_layout=L.VT_NCTHW)

@@ -8,6 +8,8 @@ pad / cast done with torch tensor ops (data movement only) and cached per (dtype
 """
 import torch
 
+from . import lib as L
+from . import ops
 from .ops import pad_channels
 
 
@@ -47,24 +49,29 @@ def pack_split3(w2d: torch.Tensor) -> torch.Tensor:
     return planes.view(SPLIT3_DTYPE).reshape(cout, Kp)
 
 
-def set_arith(root: torch.nn.Module, arith):
-    """Select the weight arithmetic of every convolution under `root` for fp32 storage: None = fp32 rows (fp32 MFMA),
-    ARITH_SPLIT3 = split-bf16 planes (three bf16 MFMAs per product).  Visits the PackedCache objects the modules hold
-    (directly or inside tuples / lists); caches created with pin_native=True (operands of an activation x activation GEMM)
-    keep fp32 rows."""
-    assert arith in (None, ARITH_SPLIT3)
-
+def packed_caches(root: torch.nn.Module):
+    """every PackedCache under `root`.  The one rule: a cache belongs to a ConvSite, and a module keeps its sites as attributes, directly
+    or inside tuples / lists"""
     def visit(v):
-        if isinstance(v, PackedCache):
-            if not v.pin_native:
-                v.arith = arith
+        if isinstance(v, ConvSite):
+            yield v.pack
         elif isinstance(v, (tuple, list)):
             for e in v:
-                visit(e)
+                yield from visit(e)
 
     for m in root.modules():
-        for v in m.__dict__.values():
-            visit(v)
+        for v in vars(m).values():
+            yield from visit(v)
+
+
+def set_arith(root: torch.nn.Module, arith):
+    """Select the weight arithmetic of every convolution under `root` for fp32 storage: None = fp32 rows (fp32 MFMA),
+    ARITH_SPLIT3 = split-bf16 planes (three bf16 MFMAs per product).  Caches created with pin_native=True (operands of an
+    activation x activation GEMM) keep fp32 rows."""
+    assert arith in (None, ARITH_SPLIT3)
+    for cache in packed_caches(root):
+        if not cache.pin_native:
+            cache.arith = arith
 
 
 def time_upsample_parity_weights(weight: torch.Tensor, early: bool):
@@ -143,8 +150,6 @@ class PackedCache:
         ent = self._entries.get(slot)
         if ent is None or ent[0] != key:
             if weight.is_cuda:
-                from . import ops
-
                 wd = weight.detach()
                 wd = wd if wd.dtype == torch.float32 and wd.is_contiguous() else wd.float().contiguous()
                 mix = None if self._mix is None else self._mix(tuple(wd.shape[2:]))
@@ -167,8 +172,6 @@ class DgradPackCache:
         self._entries = {}           # (dtype, cout_stored) -> (validity key, rows)
 
     def get(self, weight: torch.nn.Parameter, dtype, cout_stored):
-        from . import ops
-
         key = (weight.device, weight._version, weight.data_ptr())
         slot = (dtype, cout_stored)
         ent = self._entries.get(slot)
@@ -177,3 +180,33 @@ class DgradPackCache:
             wd = wd if wd.dtype == torch.float32 and wd.is_contiguous() else wd.float().contiguous()
             ent = self._entries[slot] = (key, ops.pack_conv_weight_dgrad(wd, dtype, cout_stored))
         return ent[1]
+
+
+class ConvSite:
+    """One convolution as the kernels see it: the parameter holder (nn.Conv1d / Conv2d / Conv3d, never called), the geometry of its launch and
+    the packed forms of its weight.  A plain object, built in the __init__ of the module that runs it, so it adds no state_dict key and a
+    copy of the module copies it along with the holder.  Several sites may share a holder: the parity classes of an up-sampler, the W_v
+    row operand of attention.  `clip_tmode` is the time-pad mode on a whole clip (what the training path runs); chunked passes hand `run`
+    their own mode and cache (CausalConv3d / CausalConv1d)."""
+
+    def __init__(self, conv, geom, *, clip_tmode=L.VT_TPAD_ZERO, transform=None, mix=None, pin_native=False):
+        self.conv, self.geom, self.clip_tmode = conv, geom, clip_tmode
+        self.cin, self.cout = conv.in_channels, conv.out_channels
+        self.pack = PackedCache(transform, pin_native, mix)
+        self._dgrad = None           # DgradPackCache, made by the first backward
+
+    def rows(self, dt, cin_stored):
+        """(packed weight rows, fp32 bias) alone, for the launches that are not ops.conv"""
+        return self.pack.get(self.conv.weight, self.conv.bias, dt, cin_stored=cin_stored)
+
+    def run(self, x, dt, *, tmode=L.VT_TPAD_ZERO, cache=None, **kw):
+        w, b = self.pack.get(self.conv.weight, self.conv.bias, dt, cin_stored=x.shape[-1])
+        return ops.conv(x, w, b, self.geom, cout=self.cout, tmode=tmode, cache=cache, **kw)
+
+    def run_clip(self, x, dt, **kw):
+        return self.run(x, dt, tmode=self.clip_tmode, **kw)
+
+    def dgrad_rows(self, dtype, cout_stored):
+        if self._dgrad is None:
+            self._dgrad = DgradPackCache()
+        return self._dgrad.get(self.conv.weight, dtype, cout_stored)

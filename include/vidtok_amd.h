@@ -120,6 +120,8 @@ int vt_conv_max_lds_bytes(void);
  *   conv_nt_mb (64)     outputs (y and the fused LayerNorm) of at least this many MiB are written by the LDS epilogues with streaming (nt)
  *                       stores: rows nobody reads before they have left every cache do not displace the weight slabs and halo rows the next tiles
  *                       read again (whole benchmark step - 0.7 %; the fused temporal block and conv3x3_ws2 always store this way); 0 = plain stores
+ *   conv_tup3 (1)       a causal v1.0 time up-sampler runs as vt_conv (V = W1 x) + vt_time_upsample3 (three frame products for two output
+ *                       frames) where vt_time_upsample3_supported says so; 0: it answers no, the hosts run the two parity launches (four products)
  *   attn_flash (1)      the attention block as one vt_flash_attention launch where it applies; 0: GEMM -> softmax -> GEMM operators
  *   tblock_prof_mode (0), ws_prof_mode (0)   measurement aids
  * (Rounds 1-5 also kept the superseded forms selectable -- K-step schedules 0 / 1 / 3 / 4, the first LayerNorm epilogue of the 8-wave
@@ -239,6 +241,26 @@ int vt_conv_plan(const vt_conv_desc* d, int32_t* out8);
 int vt_conv_profile(const vt_conv_desc* d, uint64_t* stamps_out, vt_stream stream);
 /* sizeof(vt_conv_desc) as compiled: lets a binding verify its struct mirror */
 int vt_conv_desc_size(void);
+
+/* ------------------------------------------------------------------------------------------
+ * vt_time_upsample3 -- the causal v1.0 time up-sampler (TimeUpsampleResCausal2x: every frame twice, causal 3 x 3 x 3 convolution,
+ * alpha-mix against the repeated input) as three frame products for two output frames.  With x[-1] = 0 the two parity launches of
+ * vt_conv (yt_mul = 2) compute o[2j] = (W0+W1) x[j-1] + W2 x[j] and o[2j+1] = W0 x[j-1] + (W1+W2) x[j]: four 3 x 3 products.
+ * Both frames share U[j] = W0 x[j-1] + W2 x[j], and W1 x[j-1] is the previous pair's W1 x[j]; with V[j] = W1 x[j], V[-1] = 0:
+ *     o[2j] = U[j] + V[j-1]        o[2j+1] = U[j] + V[j]
+ * `u` is the parity descriptor of the even frames with the weights [W0 | W2]: KT = 2, 3 x 3, pt = 1, tmode VT_TPAD_ZERO,
+ * res_mode VT_RES_MIX against x, yt_mul = 2, yt_off = 0, optionally ln_*.  `v` = V, [B][Ti][Ho][Wo][ldv] in the storage type (a
+ * plain vt_conv of x with W1, no bias).  One launch writes, for every pixel of frame j, both frames of the pair:
+ *     y[2j+q] = alpha x[j] + (1 - alpha) (acc + bias + V[j-1+q])        q = 0, 1;   V[-1] = 0 at the start of every clip
+ * and, where vt_conv_plan(u) fuses the LayerNorm (its rule for an alpha-mix launch: Cout = 256, option conv_tup_ln), also
+ * ln_out[2j+q] = [SiLU](LN(y[2j+q])) from the unrounded row.
+ * Covered (a function of one clip's geometry, the type and the options, never of B): bf16 / fp16 with results in the same type,
+ * Cout % 256 == 0 on the 256 x 256 tile, Cin % 64 == 0 and tensors below 4 GiB (the tap walk on buffer descriptors),
+ * Ho * Wo % 256 == 0, ldy / ldr / ldn (and ldv) % 8 == 0, option conv_tup3.  vt_time_upsample3_supported(u) says so without
+ * launching (1 / 0); anything else returns VT_ERR_ARG, and the host runs the two parity launches.
+ * ------------------------------------------------------------------------------------------ */
+int vt_time_upsample3_supported(const vt_conv_desc* u);
+int vt_time_upsample3(const vt_conv_desc* u, const void* v, int32_t ldv, vt_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * vt_temporal_block -- one fused launch for the temporal residual block of the reference,

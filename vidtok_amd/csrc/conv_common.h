@@ -74,6 +74,8 @@ struct ConvArgs {
   int nt_store;                // 1: the LDS epilogues write y / LayerNorm(y) with streaming (nt) stores (outputs of at least conv_nt_mb MiB)
   unsigned long long* prof;    // PROF instantiation only (vt_conv_profile): cycle stamps of workgroup 0
   int prof_mode;               // PROF instantiation of conv_ws2.hip only: option ws_prof_mode
+  const char* pair_v;          // LN256 = 2 (vt_time_upsample3) only: V = W1 x, [B][Ti][Ho][Wo][ldv] in the storage type, rows indexed like x
+  int ldv;
 };
 
 // Split-bf16 arithmetic (vt_dtype VT_BF16X3, "bf16x3"): fp32 STORAGE on both sides of the convolution, bf16 MATRIX cores

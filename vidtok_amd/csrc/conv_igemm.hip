@@ -174,6 +174,30 @@ extern "C" int vt_conv(const vt_conv_desc* d, vt_stream stream_) {
                           d->ln_eps, d->ln_mode == 2 ? 1 : 0, stream_);
 }
 
+// The three-product time up-sampler (include/vidtok_amd.h): the parity descriptor's launch on the 8-wave tile with the paired epilogue
+// (LN256 = 2 of conv_igemm_glds_kernel), which forms both frames of a pair from one accumulator row and V = W1 x.  The serving rule is
+// tup3_eligible (conv_select.h); the K loop, the tile walk, the skipped zero taps and the streaming stores are vt_conv's.
+extern "C" int vt_time_upsample3_supported(const vt_conv_desc* u) {
+  ConvArgs a;
+  ConvPlan p;
+  if (conv_decide(u, a, p) != VT_OK) return 0;
+  return tup3_eligible(u, a, p) ? 1 : 0;
+}
+
+extern "C" int vt_time_upsample3(const vt_conv_desc* u, const void* v, int32_t ldv, vt_stream stream_) {
+  ConvArgs a;
+  ConvPlan p;
+  const int rc = conv_decide(u, a, p);
+  if (rc != VT_OK) return rc;
+  VT_CHECK_ARG(tup3_eligible(u, a, p), "vt_time_upsample3: descriptor not covered (ask vt_time_upsample3_supported; the parity launches of vt_conv serve it)");
+  VT_CHECK_ARG(v != nullptr && (reinterpret_cast<uintptr_t>(v) & 15) == 0 && ldv >= u->Cout && ldv % 8 == 0,
+               "vt_time_upsample3: v must be 16-byte aligned with ldv = %d >= Cout and a multiple of 8", ldv);
+  a.pair_v = reinterpret_cast<const char*>(v);
+  a.ldv = ldv;
+  const IgemmVariant pair = {TILE_256x256, true, 2, 2, kRowBytes};
+  return launch_igemm(u->dtype, false, a, pair, 1, stream_);
+}
+
 // vt_conv with a ReLU epilogue (VGG16's conv + ReLU pairs, LPIPS): the same descriptor checks, then the ACT = VT_ACT_RELU instantiations of
 // conv_igemm_act.hip -- never the weight-stationary, conv_in8, narrow or split-K kernels, whose epilogues have no activation
 extern "C" int vt_conv_act(const vt_conv_desc* d, int32_t act, vt_stream stream_) {

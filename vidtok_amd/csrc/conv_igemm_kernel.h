@@ -459,6 +459,134 @@ __device__ __forceinline__ void conv_epilogue_lds256(const ConvArgs& p, f32x16 (
   half(std::integral_constant<int, 1>{});
 }
 
+// Paired epilogue of the causal v1.0 time up-sampler in its three-product form (vt_time_upsample3; LN256 = 2, 16-bit types).  The launch
+// convolves [W0 | W2] over (x[j-1], x[j]): the accumulator row of frame j is U[j], shared by both output frames of the pair, and with
+// V = W1 x (a plain launch of its own, p.pair_v, rows indexed like x)
+//   y[2j + q] = alpha x[j] + (1 - alpha) (U[j] + bias + V[j - 1 + q]),   q = 0, 1,   V[-1] = 0 at the start of every clip
+// -- three frame products for two frames where the two parity launches ran four.  The transposition, the lane -> (row, 8 channels)
+// map, the row arithmetic and the LayerNorm are those of conv_epilogue_lds256; every T row is read once and leaves as two y rows (and
+// two LayerNorm rows, each from its own unrounded row).  A tile lies in one frame (the serving rule, conv_select.h), so "first frame of
+// a clip" is uniform.  The V rows of a half are requested inside the row loop in two batches of four rows (beside the eight mix rows
+// requested up front: all sixteen at once would not fit the registers while the second half's accumulators are live).
+template <typename TOut>
+__device__ __forceinline__ void conv_epilogue_lds256_pair(const ConvArgs& p, f32x16 (&acc)[4][2], int m_blk, int n_blk, int wm, int wn, int lane,
+                                                          int tid, char* smem) {
+#pragma clang fp contract(off)
+  static_assert(sizeof(TOut) == 2, "paired epilogue: 16-bit storage");
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  TOut* __restrict__ yg = reinterpret_cast<TOut*>(p.y);
+  const TOut* __restrict__ rg = reinterpret_cast<const TOut*>(p.res);
+  const TOut* __restrict__ vg = reinterpret_cast<const TOut*>(p.pair_v);
+  TOut* __restrict__ ng = reinterpret_cast<TOut*>(p.ln_out);
+  float* T = reinterpret_cast<float*>(smem);
+  const bool has_ln = p.ln_mode != 0;                    // uniform
+  const float alpha = 1.0f / (1.0f + __expf(-p.mix_factor[0]));
+  constexpr int RS = 16;
+  const int j = tid & 31, rsub = tid >> 5;
+  const long long hw = (long long)p.Ho * p.Wo;
+  const unsigned frame = fast_div((unsigned)m_blk, p.fd_hw);                      // b * To + t of the whole tile
+  const bool has_prev = frame != fast_div(frame, p.fd_to) * (unsigned)p.To;      // t > 0: V[j-1] exists
+  const long long row0 = (long long)frame * hw;                                  // output row of pixel m, frame 2j: m + frame * hw
+  f32x2 lg[4], lb[4];
+  if (has_ln) {
+    const f32x4 g0 = *reinterpret_cast<const f32x4*>(p.ln_gamma + 8 * j), g1 = *reinterpret_cast<const f32x4*>(p.ln_gamma + 8 * j + 4);
+    const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.ln_beta + 8 * j), b1 = *reinterpret_cast<const f32x4*>(p.ln_beta + 8 * j + 4);
+    lg[0] = f32x2{g0[0], g0[1]}; lg[1] = f32x2{g0[2], g0[3]}; lg[2] = f32x2{g1[0], g1[1]}; lg[3] = f32x2{g1[2], g1[3]};
+    lb[0] = f32x2{b0[0], b0[1]}; lb[1] = f32x2{b0[2], b0[3]}; lb[2] = f32x2{b1[0], b1[1]}; lb[3] = f32x2{b1[2], b1[3]};
+    if (p.ln_mode == 2) {                                  // SiLU: the affine carries -log2(e) (ln_row8, common.h)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        lg[q] = lg[q] * kNegLog2e;
+        lb[q] = lb[q] * kNegLog2e;
+      }
+    }
+  }
+  // one output row: the mix against x[j], the store, the LayerNorm of the unrounded row (one-pass form, as conv_epilogue_lds256)
+  auto emit = [&](const f32x2 (&t)[4], const Oct<TOut>& vq, const Oct<TOut>& xq, long long orow) {
+    f32x2 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      v[q] = t[q] + f32x2{vq.get(2 * q), vq.get(2 * q + 1)};
+      v[q] = f32x2{xq.get(2 * q), xq.get(2 * q + 1)} * alpha + v[q] * (1.0f - alpha);
+    }
+    if (p.ln_keep_y || !has_ln) {
+      const float yv[8] = {v[0][0], v[0][1], v[1][0], v[1][1], v[2][0], v[2][1], v[3][0], v[3][1]};
+      Oct<TOut>::store(yg + orow * p.ldy + n_blk + 8 * j, yv, p.nt_store != 0);
+    }
+    if (!has_ln) return;
+    float o[8];
+    const f32x2 s = (v[0] + v[1]) + (v[2] + v[3]);
+    f32x2 qq = v[0] * v[0];
+#pragma unroll
+    for (int q = 1; q < 4; ++q) qq = __builtin_elementwise_fma(v[q], v[q], qq);
+    float nm;
+    const float rstd = ln_row_stats<32>(s[0] + s[1], qq[0] + qq[1], p.ln_eps, &nm);
+    const f32x2 rstd2 = {rstd, rstd}, nm2 = {nm, nm}, c2 = {kNegLog2e, kNegLog2e};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      f32x2 u = __builtin_elementwise_fma(__builtin_elementwise_fma(v[q], rstd2, nm2), lg[q], lb[q]);
+      if (p.ln_mode == 2) {
+        const f32x2 den = __builtin_elementwise_fma(f32x2{__builtin_amdgcn_exp2f(u[0]), __builtin_amdgcn_exp2f(u[1])}, c2, c2);
+        u = u * f32x2{__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
+      }
+      o[2 * q] = u[0];
+      o[2 * q + 1] = u[1];
+    }
+    Oct<TOut>::store(ng + orow * p.ldn + 8 * j, o, p.nt_store != 0);
+  };
+  const int h = lane >> 5;
+  auto half = [&](auto pz_c) {
+    constexpr int PZ = decltype(pz_c)::value;            // compile-time: acc[.][PZ] must not become a dynamic register index
+    // tile pixel of T row r = rsub + RS it:  (r >> 5) * 64 + PZ * 32 + (r & 31)
+    Oct<TOut> xq[8];
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const long long m = (long long)m_blk + ((RS * it) >> 5) * 64 + PZ * 32 + rsub + ((RS * it) & 31);
+      xq[it].load(rg + m * p.ldr + n_blk + 8 * j);
+    }
+    __syncthreads();                                    // K loop / previous half: everybody is done with this LDS
+    {
+      const int prl = wm * 32 + (lane & 31);
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int c = wn * 128 + 32 * a + 8 * g + 4 * h;
+          f32x4 bq;
+          if (p.bias) bq = *reinterpret_cast<const f32x4*>(p.bias + n_blk + c);
+          else bq[0] = bq[1] = bq[2] = bq[3] = 0.0f;
+          f32x4 v;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = acc[a][PZ][4 * g + e] + bq[e];
+          *reinterpret_cast<f32x4*>(T + prl * 256 + (((c >> 2) ^ (prl & 63)) << 2)) = v;
+        }
+    }
+    __syncthreads();
+    Oct<TOut> vp[4], vc[4];                              // V[j-1], V[j] of four rows
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      if ((it & 3) == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const long long m = (long long)m_blk + ((RS * (it + k)) >> 5) * 64 + PZ * 32 + rsub + ((RS * (it + k)) & 31);
+          vc[k].load(vg + m * p.ldv + n_blk + 8 * j);
+          if (has_prev) vp[k].load(vg + (m - hw) * p.ldv + n_blk + 8 * j);
+          else vp[k].w = u32x4{0u, 0u, 0u, 0u};
+        }
+      }
+      const int r = rsub + RS * it;
+      const long long m = (long long)m_blk + ((RS * it) >> 5) * 64 + PZ * 32 + rsub + ((RS * it) & 31);
+      const f32x4 t0 = *reinterpret_cast<const f32x4*>(T + r * 256 + (((2 * j) ^ (r & 63)) << 2));
+      const f32x4 t1 = *reinterpret_cast<const f32x4*>(T + r * 256 + (((2 * j + 1) ^ (r & 63)) << 2));
+      const f32x2 t[4] = {f32x2{t0[0], t0[1]}, f32x2{t0[2], t0[3]}, f32x2{t1[0], t1[1]}, f32x2{t1[2], t1[3]}};
+      emit(t, vp[it & 3], xq[it], m + row0);
+      emit(t, vc[it & 3], xq[it], m + row0 + hw);
+    }
+  };
+  half(std::integral_constant<int, 0>{});
+  half(std::integral_constant<int, 1>{});
+}
+
 // ------------------------------------------------------------------------------------------------
 // The operand tiles go global -> LDS with LDS-DMA (no VGPR round trip, no ds_write pass -- a
 // register-staged first version spent ~415 LDS cycles per K step on ds_write_b128 against 512 MFMA cycles).  The DMA writes each wave's 64
@@ -486,7 +614,9 @@ __device__ __forceinline__ void conv_epilogue_lds256(const ConvArgs& p, f32x16 (
 // LN256  1: the 8-wave tile with the LDS-transposed epilogue (conv_epilogue_lds256: LayerNorm, or plain coalesced rows) -- its own
 //        instantiations: the mere presence of a second epilogue path slowed every 256-tile convolution by 8 % through
 //        register allocation (round 1)
-// SCHED  K-step schedule of the 8-wave tile on descriptors: 0 plain loop (also every 4-wave tile and the pointer form), 1 software-
+//        2: the same K loop with the paired epilogue of the three-product time up-sampler (conv_epilogue_lds256_pair; vt_time_upsample3,
+//        bf16 / fp16 only) -- again its own instantiations, for the same reason
+// SCHED K-step schedule of the 8-wave tile on descriptors: 0 plain loop (also every 4-wave tile and the pointer form), 1 software-
 //        pipelined single body (fp32 operands), 2 two-group ping-pong (16-bit operands), 5 two groups for the split-bf16 arithmetic
 // ACT    activation of the epilogue, applied to the fp32 result before the rounding to TOut: 0 none (every vt_conv instantiation),
 //        VT_ACT_RELU (vt_conv_act, conv_igemm_act.hip) -- a compile-time variant, so the K loop and the epilogues of ACT = 0 are untouched
@@ -1310,7 +1440,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_igemm_glds_ker
     static_assert(WAVES_M == 4 && WAVES_N == 2 && TM == 2 && TN == 4 && std::is_same<typename storage_of<MT>::type, TOut>::value, "LN256: the 8-wave 256 x 256 tile");
     static_assert(STAGES * STAGE_BYTES >= 128 * 256 * 4, "LN256: the transposition tile must fit the ring");
     if constexpr (!BUF) wait_vmcnt<0>();
-    conv_epilogue_lds256<TOut, ACT>(p, acc, m_blk, n_blk, wm, wn, lane, tid, smem, z);
+    if constexpr (LN256 == 2) {
+      static_assert(ACT == 0 && is_h16<MT>::value, "LN256 = 2: the paired epilogue of vt_time_upsample3, 16-bit types");
+      conv_epilogue_lds256_pair<TOut>(p, acc, m_blk, n_blk, wm, wn, lane, tid, smem);
+    } else {
+      conv_epilogue_lds256<TOut, ACT>(p, acc, m_blk, n_blk, wm, wn, lane, tid, smem, z);
+    }
     return;
   }
   if constexpr (WAVES_M == 2 && WAVES_N == 2 && TM == 2 && TN == 2 && STAGES * STAGE_BYTES >= 128 * 128 * 4) {
@@ -1358,7 +1493,7 @@ int launch_variant(const ConvArgs& a_in, int nbatch, hipStream_t stream) {
   const unsigned long long cb = a.tmode == VT_TPAD_CACHE ? (unsigned long long)a.B * a.ncache * a.Hi * a.Wi * a.Cin * sizeof(MT) : 0ull;
   const bool cache_ok = a.tmode != VT_TPAD_CACHE ||
                         (FAST && (nbatch == 1 || a.ksplit) && a.prof == nullptr && cb < 0xFFFF0000ull && ((long long)a.Ho * a.Wo) % BM == 0 && a.ups_t == 0);
-  const bool buf = conv_buf() && xb < 0xFFFF0000ull && wb < 0xFFFF0000ull && cache_ok &&
+  const bool buf = desc_gather_fits(a, (int)sizeof(MT)) && cache_ok &&
                    a.KH <= 8 && a.KW <= 8;   // the per-row padding mask of the FAST form holds 8 bits per axis
   VT_CHECK_ARG(!a.ksplit || buf, "vt_conv: split-K needs the descriptor gather");
   // zero-padded time taps skipped per tile: the tap-walk form on descriptors, a tile inside one output frame
@@ -1372,12 +1507,15 @@ int launch_variant(const ConvArgs& a_in, int nbatch, hipStream_t stream) {
   constexpr int SCHED_BUF = !(EIGHT && FAST) ? 0
                             : (is_split3<MT>::value ? ((ROWB == 64 && STAGES == 4) ? 5 : 0)
                                : ((ROWB == kRowBytes && STAGES == 2) ? (is_h16<MT>::value ? 2 : 1) : 0));
-  const void* kern;
+  const void* kern = nullptr;
   if (buf) {
     a.x_bytes = (unsigned)xb;
     a.w_bytes = (unsigned)wb;
     a.c_bytes = (unsigned)cb;
     kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, true, LN256, false, SCHED_BUF, ACT>);
+  } else if constexpr (LN256 == 2) {
+    // the paired launch exists on descriptors only (tup3_eligible asks for them: desc_gather_fits, conv_select.h); no pointer-form instantiation
+    VT_CHECK_ARG(false, "vt_time_upsample3: the descriptor gather is required (option conv_buf, tensors below 4 GiB)");
   } else {
     kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, false, LN256, false, 0, ACT>);
   }
@@ -1435,6 +1573,12 @@ int dispatch_tile(const ConvArgs& a, const IgemmVariant& v, int nbatch, hipStrea
           return v.ln256 ? launch_tile<MT, TOut, TILE_256x256, true, 1, 4, 64>(a, nbatch, stream) : launch_tile<MT, TOut, TILE_256x256, true, 0, 4, 64>(a, nbatch, stream);
         }
       } else if constexpr (std::is_same<MT, TOut>::value) {
+        if constexpr (is_h16<MT>::value) {
+          if (v.ln256 == 2) {  // conv_epilogue_lds256_pair: both frames of a time up-sampler pair from one accumulator row (vt_time_upsample3)
+            VT_CHECK_VARIANT(v.fast && v.stages == 2 && v.rowb == kRowBytes && a.pair_v != nullptr);
+            return launch_tile<MT, TOut, TILE_256x256, true, 2>(a, nbatch, stream);
+          }
+        }
         if (v.ln256) {         // conv_epilogue_lds256: fused LayerNorm, or ln_mode = 0 for coalesced rows
           VT_CHECK_VARIANT(v.fast && v.stages == 2 && v.rowb == kRowBytes);
           return launch_tile<MT, TOut, TILE_256x256, true, 1>(a, nbatch, stream);

@@ -1,7 +1,8 @@
 // Which kernel / tile / epilogue / ring a vt_conv call gets.  conv_decide makes the decision ONCE per call, as a ConvPlan: vt_conv runs the
 // plan, vt_conv_plan reports it, vt_conv_work_bytes / vt_conv_profile / vt_conv_act read it (conv_igemm.hip), and the per-type translation
 // units that hold the kernel instantiations (conv_igemm_{f32,bf16,f16,x3,act}.hip) switch on its IgemmVariant.  The *_eligible predicates
-// are pure functions of the descriptor (ConvArgs) and of the option table; conv_decide is their only caller.
+// are pure functions of the descriptor (ConvArgs) and of the option table; conv_decide is their only caller -- but for tup3_eligible, the
+// rule of the paired time up-sampler launch, which vt_time_upsample3 / vt_time_upsample3_supported apply to conv_decide's result.
 #pragma once
 #include "conv_common.h"
 
@@ -87,6 +88,18 @@ inline bool narrow_eligible(const ConvArgs& a, int nbatch, int dtype, int out_dt
   return true;
 }
 
+// the 8-wave 256 x 256 tile for a layer of `tiles` such tiles: at least conv_tile_min (default 128), or forced / forbidden by conv_tile
+inline bool tile256_wanted(long long tiles) {
+  const int force = vt_opt(OPT_CONV_TILE);
+  return force != 128 && (tiles >= vt_opt(OPT_CONV_TILE_MIN) || force == 256);
+}
+
+// the gather through buffer descriptors (option conv_buf): both operands below 4 GiB minus the out-of-range marker
+inline bool desc_gather_fits(const ConvArgs& a, int elem_bytes) {
+  const unsigned long long xb = (unsigned long long)a.B * a.Ti * a.Hi * a.Wi * a.Cin * elem_bytes, wb = (unsigned long long)a.Cout * a.ldw * elem_bytes;
+  return conv_buf() && xb < 0xFFFF0000ull && wb < 0xFFFF0000ull;
+}
+
 inline TileKind select_tile(const ConvArgs& a, int nbatch) {
   auto blocks = [&](int bm, int bn) {
     return (long long)((a.M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn) * nbatch;
@@ -94,10 +107,9 @@ inline TileKind select_tile(const ConvArgs& a, int nbatch) {
   const bool vec_epi = a.out_layout == VT_NDHWC && (a.ldy & 3) == 0 && (a.res_mode == VT_RES_NONE || (a.ldr & 3) == 0);
   if (a.Cout <= 32) return TILE_256x32;
   if (a.Cout <= 64) return TILE_256x64;
-  const int force = vt_opt(OPT_CONV_TILE);
   // at least conv_tile_min (default 128) tiles: with the scheduled K loops even half-filled single rounds of the 8-wave
   // tile beat 1.25 rounds of 128 x 128 tiles (M = 20 480, Cout = 512: 0.143 -> 0.121 ms at K = 4 608, 0.38 -> 0.29 at 13 824)
-  if (a.Cout % 256 == 0 && vec_epi && force != 128 && (blocks(256, 256) >= vt_opt(OPT_CONV_TILE_MIN) || force == 256)) return TILE_256x256;
+  if (a.Cout % 256 == 0 && vec_epi && tile256_wanted(blocks(256, 256))) return TILE_256x256;
   return TILE_128x128;
 }
 
@@ -150,6 +162,32 @@ inline int splitk_planes(const vt_conv_desc* d, const ConvArgs& a, const ConvPla
   // alone it would leave every workgroup by itself on a CU walking the whole K -- whatever the batch around it.
   const long long clip_tiles = (((long long)a.To * a.Ho * a.Wo + 127) / 128) * ((a.Cout + 127) / 128);
   return clip_tiles <= device_cus() ? 3 : 0;
+}
+
+// Paired launch of the three-product time up-sampler (vt_time_upsample3; conv_epilogue_lds256_pair): is the parity descriptor `d` --
+// already validated by conv_decide into (a, p) -- served?  Like splitk_planes a function of ONE CLIP's geometry, the type and the
+// options, never of B: the paired launch rounds V = W1 x once more than the two parity launches, so a rule that counted the launch's
+// tiles would tie a clip's bits to its batch.  16-bit storage = arithmetic type; the even-frame parity descriptor (k = 2 in time over
+// 3 x 3, causal zero padding, alpha-mix against x, frames interleaved by 2); the 256 x 256 tile in the tap-walk form on buffer
+// descriptors with the LDS epilogue's 16-byte rows; a tile inside one frame (the epilogue reads V[j-1] / V[j] and "first frame of the
+// clip" per tile).  A LayerNorm is taken exactly where conv_decide fuses it into an alpha-mix launch (Cout = 256, option conv_tup_ln);
+// one it does not fuse never gets here (conv_decide rejects the LayerNorm of an interleaved output outside an epilogue).
+inline bool tup3_eligible(const vt_conv_desc* d, const ConvArgs& a, const ConvPlan& p) {
+  if (vt_opt(OPT_CONV_TUP3) == 0 || a.prof != nullptr) return false;
+  const bool h16_io = vt_is_h16(d->dtype) && d->out_dtype == d->dtype;
+  if (a.KT != 2 || a.KH != 3 || a.KW != 3 || a.st != 1 || a.sh != 1 || a.sw != 1 || a.pt != 1 || a.ph != 1 || a.pw != 1) return false;
+  if (a.tmode != VT_TPAD_ZERO || a.ups_t || a.ups_s || a.To != a.Ti || a.Ho != a.Hi || a.Wo != a.Wi) return false;
+  if (a.yt_mul != 2 || a.yt_base != 0 || a.ys_mul == 2 || a.res_mode != VT_RES_MIX) return false;
+  if (d->ln_mode != 0 && (!p.ln_fused || (a.ldn & 7) != 0)) return false;
+  // the LDS epilogue's own conditions (16-bit rows of 16 bytes, full tiles, the tap walk, the mix operand indexed like the result) ...
+  ConvArgs e = a;
+  e.ln_mode = 0;
+  if (!lds256_plain_eligible(e, p.nbatch, h16_io)) return false;
+  // ... on descriptors (launch_variant refuses the paired instantiation otherwise), a tile inside one frame, and the 8-wave tile by
+  // select_tile's rule applied to one clip's pixels
+  const long long hw = (long long)a.Ho * a.Wo;
+  if (!desc_gather_fits(a, 2) || hw % 256 != 0) return false;
+  return tile256_wanted((a.To * hw / 256) * (a.Cout / 256));
 }
 
 // vt_conv's decision, made once: argument validation, the kernel's view of the descriptor (`a`) and the plan, in the order vt_conv applies

@@ -98,6 +98,7 @@ struct Act {                       // an activation, optionally with the LayerNo
   const Norm* norm = nullptr;
   bool silu = false;
   bool has_n() const { return norm != nullptr; }
+  bool tup3 = false;               // answer of a ConvOpts::tup3_probe call: vt_time_upsample3 serves the descriptor
 };
 struct NormRef {
   const Norm* norm = nullptr;
@@ -298,6 +299,25 @@ std::vector<float> xf_time_parity(const Param& p, std::vector<int64_t>& shape, i
   shape[2] = 2;
   return o;
 }
+// the three-product form of the causal time up-sampler (packing.py::time_upsample3_weights): part 2 = [W0, W2] (the k = 2 window of U),
+// part 3 = W1 alone (V, a per-frame convolution); single taps, nothing summed.  (The part numbers continue xf_time_parity's 0 / 1:
+// conv_w keys a packed weight by the transform's arguments.)
+std::vector<float> xf_time_up3(const Param& p, std::vector<int64_t>& shape, int part, int) {
+  const int64_t co = shape[0], ci = shape[1], hw = shape[3] * shape[4];
+  const int kt = part == 2 ? 2 : 1;
+  std::vector<float> o((size_t)co * ci * kt * hw);
+  for (int64_t a = 0; a < co * ci; ++a)
+    for (int64_t s = 0; s < hw; ++s) {
+      if (part == 2) {
+        o[(a * 2 + 0) * hw + s] = p.data[(a * 3 + 0) * hw + s];
+        o[(a * 2 + 1) * hw + s] = p.data[(a * 3 + 2) * hw + s];
+      } else {
+        o[a * hw + s] = p.data[(a * 3 + 1) * hw + s];
+      }
+    }
+  shape[2] = kt;
+  return o;
+}
 // space: [Co][Ci][3][3] -> [Co][Ci][2][2]; rows [W0, W1+W2] for py = 0, [W0+W1, W2] for py = 1, likewise columns
 std::vector<float> xf_space_parity(const Param& p, std::vector<int64_t>& shape, int py, int px) {
   const int64_t n = shape[0] * shape[1];
@@ -391,6 +411,8 @@ struct ConvOpts {
   Tens* ln_out = nullptr;          // ... and its normalised twin (the emitted LayerNorm of an interleaved output)
   bool ln_optional = false;        // emit `ln` only if this launch's epilogue takes it (vt_conv_plan), else run without (ops.conv ln_optional)
   bool plan_only = false;          // with ln_optional: launch nothing, only answer (Act::has_n) whether the epilogue would take the LayerNorm
+  bool tup3_probe = false;         // with plan_only: also answer (Act::tup3) whether vt_time_upsample3 serves this parity descriptor
+  const Tens* tup3_v = nullptr;    // run as the paired launch vt_time_upsample3 with this V = W1 x (the descriptor was probed before)
   int yt_mul = 1, yt_off = 0, ys = 0, ys_oh = 0, ys_ow = 0;
   float* ncthw = nullptr;          // write fp32 NCTHW here instead
   int t_trim = 0;
@@ -465,7 +487,17 @@ Act conv(Ctx& c, const Tens& x, const void* w, int ldw, const float* bias, const
       r.n = Tens(); r.norm = nullptr;
     }
   }
+  if (o.tup3_probe) {
+    vt_conv_desc q = d;
+    standins(q);
+    if (q.ln_mode != 0 && q.ln_out == nullptr) q.ln_out = (void*)16;
+    r.tup3 = vt_time_upsample3_supported(&q) == 1;
+  }
   if (o.plan_only) return r;
+  if (o.tup3_v) {
+    if (!c.dry) M_CALL(vt_time_upsample3(&d, o.tup3_v->p, o.tup3_v->ld, c.stream));
+    return r;
+  }
   // split-K over the time taps (small-M launches): the library says how much scratch; it comes from the stage's arena.
   {
     vt_conv_desc q = d;
@@ -902,6 +934,33 @@ struct TimeUp : Stage {            // TimeUpsampleResCausal2x: v1.0 nearest as t
     const float* mf = c.m->f32(key + ".mix_factor", c.dry);
     const bool nc = c.m->noncausal();
     const std::string ck = key + ".conv" + c.m->cv();
+    if (!nc) {
+      // three frame products instead of four (vt_time_upsample3; time_parity_upsample of the Python host): U[j] = W0 x[j-1] + W2 x[j] is
+      // shared by the two frames of a pair, V[j] = W1 x[j] by neighbouring pairs -- o[2j] = U[j] + V[j-1], o[2j+1] = U[j] + V[j].
+      // Asked with the LayerNorm the launch would really carry, before anything is allocated or packed.
+      ConvOpts o;
+      Tens probe = r.y;
+      probe.p = nullptr;
+      o.out = &r.y; o.yt_mul = 2; o.yt_off = 0; o.plan_only = true; o.tup3_probe = true;
+      if (emit_ln) { o.ln = next; o.ln_out = &probe; o.ln_optional = true; }
+      o.res = &xp; o.res_mode = VT_RES_MIX; o.mix = mf;
+      const Act q = conv(c, xp, (const void*)16, 18 * xp.ld, nullptr, g, ch, o);
+      if (q.tup3) {
+        Geom gv;
+        gv.kh = 3; gv.kw = 3; gv.ph = 1; gv.pw = 1; gv.ph_hi = 1; gv.pw_hi = 1;
+        const Act v = conv(c, xp, c.m->conv_w(ck + ".weight", xp.ld, c.dry, xf_time_up3, 3, 0), 9 * xp.ld, nullptr, gv, ch, ConvOpts());
+        ConvOpts u;
+        u.out = &r.y; u.yt_mul = 2; u.yt_off = 0; u.tup3_v = &v.y;
+        u.res = &xp; u.res_mode = VT_RES_MIX; u.mix = mf;
+        if (q.has_n()) {
+          nbuf = c.alloc(xp.B, 2 * xp.T, xp.H, xp.W, pad8(ch), c.m->dt, ch);
+          u.ln = next; u.ln_out = &nbuf;
+        }
+        conv(c, xp, c.m->conv_w(ck + ".weight", xp.ld, c.dry, xf_time_up3, 2, 0), 18 * xp.ld, c.m->f32(ck + ".bias", c.dry), g, ch, u);
+        if (q.has_n()) { r.n = nbuf; r.norm = next.norm; r.silu = next.silu; }
+        return r;
+      }
+    }
     if (emit_ln) {
       // ask before allocating the twin (a launch that refuses -- the 512-channel up-sampler always does -- left a full-size
       // buffer in the arena's peak): the decision depends on the geometry only, the same for both parity launches

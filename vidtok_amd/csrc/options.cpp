@@ -23,6 +23,7 @@ const OptDef kDefs[OPT_COUNT] = {
     {"tblock_fused", 1},    {"tblock_prof_mode", 0},
     {"conv_deep", 1},       {"ws_prof_mode", 0},    {"attn_flash", 1},      {"conv_splitk", 1},
     {"conv_tskip", 1},      {"conv_in8", 1},        {"conv_tup_ln", 1},     {"conv_nt_mb", 64},
+    {"conv_tup3", 1},
 };
 std::atomic<int> g_val[OPT_COUNT];
 std::once_flag g_once;

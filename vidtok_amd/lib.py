@@ -160,6 +160,8 @@ SIGNATURES = {
     "vt_conv_work_bytes": (_I64, [C.POINTER(ConvDesc)]),
     "vt_conv_plan": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(_I32)]),
     "vt_conv_profile": (C.c_int, [C.POINTER(ConvDesc), _P, _P]),
+    "vt_time_upsample3_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "vt_time_upsample3": (C.c_int, [C.POINTER(ConvDesc), _P, _I32, _P]),
     "vt_frames_work_floats": (_I64, [_I32, _I32, _I32]),
     "vt_frames_u8_to_ncthw": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "vt_ncthw_to_frames_u8": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P]),

@@ -24,8 +24,8 @@ import torch.nn as nn
 from . import lib as L
 from . import ops
 from .ops import ConvGeom
-from .packing import (ConvSite, space_upsample_parity_mix, space_upsample_parity_weights, time_upsample_parity_mix,
-                      time_upsample_parity_weights)
+from .packing import (ConvSite, space_upsample_parity_mix, space_upsample_parity_weights, time_upsample3_mix, time_upsample3_weights,
+                      time_upsample_parity_mix, time_upsample_parity_weights)
 
 
 def _check_norm(norm_type):
@@ -350,9 +350,11 @@ def time_parity_class(conv, geom, early):
                     mix=functools.partial(time_upsample_parity_mix, early=early))
 
 
-def time_parity_upsample(sites, x, dt, mix_factor, next_norm):
+def time_parity_upsample(sites, x, dt, mix_factor, next_norm, tup3=None):
     """alpha * up(x) + (1 - alpha) * conv(up(x)) for up = every frame twice, as the two launches of `sites` (even frames, odd frames): each
-    writes its frames of the interleaved output; the mix operand up(x)[2j+p] is x[j]."""
+    writes its frames of the interleaved output; the mix operand up(x)[2j+p] is x[j].
+    tup3 = (U site, V site) of a causal up-sampler: where vt_time_upsample3_supported says so, V = W1 x as a plain convolution and then ONE
+    paired launch that writes both frames of every pair (three frame products instead of the parity launches' four)."""
     B, T, H, W, _C = x.shape
     cout = sites[0].cout
     ld = ops.pad_channels(cout)
@@ -365,6 +367,12 @@ def time_parity_upsample(sites, x, dt, mix_factor, next_norm):
     def alloc_n():           # the LayerNorm twin, allocated by ops.conv only once vt_conv_plan says the launch emits it (pad lanes as y's)
         return (torch.empty if ld == cout else torch.zeros)(y.shape, dtype=dt, device=x.device)
 
+    if tup3 is not None:
+        su, sv = tup3
+        r = ops.time_upsample3(x, lambda: su.rows(dt, x.shape[-1]), lambda: sv.run(x, dt), mix_factor, y, cout=cout,
+                               **(dict(ln=emit["ln"], ln_out=alloc_n) if emit else {}))
+        if r is not None:
+            return Normed(y, r[1], next_norm[0], next_norm[1]) if isinstance(r, tuple) else y
     for par, site in enumerate(sites):
         r = site.run(x, dt, res=x, res_mode=L.VT_RES_MIX, mix_factor=mix_factor, out=y, out_t=(2, par),
                      **(dict(emit, ln_out=(alloc_n if n is None else n), ln_optional=True) if emit else {}))
@@ -396,6 +404,13 @@ class TimeUpsampleResCausal2x(nn.Module):
         #   o[2j] = (W0+W1) x[j-1] + W2 x[j]      o[2j+1] = W0 x[j-1] + (W1+W2) x[j]
         g = ConvGeom(kt=2, kh=3, kw=3, pt=1, ph=1, pw=1, ph_hi=1, pw_hi=1)
         self.parity_sites = (time_parity_class(self.conv.conv, g, early=True), time_parity_class(self.conv.conv, g, early=False))
+        # ... or, sharing U[j] = W0 x[j-1] + W2 x[j] between the two frames and V[j] = W1 x[j] between neighbouring pairs (three products):
+        #   o[2j] = U[j] + V[j-1]                 o[2j+1] = U[j] + V[j]                 (vt_time_upsample3; option conv_tup3)
+        self.tup3_sites = (ConvSite(self.conv.conv, ops.TUP3_GEOM, transform=functools.partial(time_upsample3_weights, part="u"),
+                                    mix=functools.partial(time_upsample3_mix, part="u")),
+                           ConvSite(self.conv.conv, ConvGeom(kh=3, kw=3, ph=1, pw=1, ph_hi=1, pw_hi=1), bias=False,
+                                    transform=functools.partial(time_upsample3_weights, part="v"),
+                                    mix=functools.partial(time_upsample3_mix, part="v")))
 
     def _interp_v11(self, x):
         n, T = self.num_temp_upsample, x.shape[1]
@@ -431,7 +446,7 @@ class TimeUpsampleResCausal2x(nn.Module):
         x = plain(x)
         mf = self.mix_factor.detach()
         if self.version == "v1_0":
-            return time_parity_upsample(self.parity_sites, x, dt, mf, next_norm)
+            return time_parity_upsample(self.parity_sites, x, dt, mf, next_norm, tup3=self.tup3_sites)
         xi = self._interp_v11(x)
         return _wrap(self.conv.run(xi, dt, res=xi, res_mode=L.VT_RES_MIX, mix_factor=mf, **_emit(next_norm)), next_norm)
 

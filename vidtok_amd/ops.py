@@ -31,6 +31,19 @@ def _conv_launch(lib, d, what, keep=()):
         CONV_RECORD.append((d, keep, (d.B * d.To * d.Ho * d.Wo * max(1, d.nbatch), d.Cout, d.KT * d.KH * d.KW * d.Cin)))
 
 
+class TimeUp3Desc(L.ConvDesc):
+    """the descriptor of a vt_time_upsample3 launch as the launch record keeps it: the parity descriptor `u` (every field vt_conv_plan reads)
+    plus the V operand, so that the launch can be replayed and priced"""
+
+    v_ptr = None
+    ldv = 0
+
+
+def time_upsample3_supported(d) -> bool:
+    """vt_time_upsample3_supported: does the paired launch serve the parity descriptor `d` (kt = 2, yt_mul = 2, alpha-mix against x)?"""
+    return bool(L.load().vt_time_upsample3_supported(C.byref(d)))
+
+
 def conv_plan(d):
     """vt_conv_plan(d) -> dict(tile=(BM, BN), waves, workgroups, ln_fused, launches, kernel="igemm" | "ws2" | "narrow" | "in8",
     lds_epilogue, deep_ring)"""
@@ -53,6 +66,9 @@ def replay_convs(record, conv_kernel_only=True):
             _, q, k, vT, bias, o, scale = d
             L.check(lib.vt_flash_attention(_ptr(q), _ptr(k), _ptr(vT), _ptr(bias), _ptr(o), _DT[q.dtype], q.shape[0], q.shape[1], q.shape[2],
                                            vT.shape[2], scale, _stream()), "vt_flash_attention(replay)")
+            continue
+        if isinstance(d, TimeUp3Desc):           # the paired launch of a time up-sampler (its LayerNorm, if any, is always the epilogue's)
+            L.check(lib.vt_time_upsample3(C.byref(d), C.c_void_p(d.v_ptr), d.ldv, _stream()), "vt_time_upsample3(replay)")
             continue
         if conv_kernel_only and d.ln_mode != 0 and not conv_plan(d)["ln_fused"]:
             d2 = L.ConvDesc()
@@ -216,6 +232,73 @@ def conv(x, w, bias, geom: ConvGeom, *, cout: int, out_dtype=None, tmode=L.VT_TP
     return (y, n) if ln_keep_y else n
 
 
+TUP3_GEOM = ConvGeom(kt=2, kh=3, kw=3, pt=1, ph=1, pw=1, ph_hi=1, pw_hi=1)    # the window (x[j-1], x[j]) of a causal time up-sampler's U term
+
+
+def time_upsample3(x, wu, v, mix_factor, out, *, cout: int, ln=None, ln_out=None):
+    """vt_time_upsample3: out[2j+q] = alpha x[j] + (1 - alpha) (conv([W0 | W2])(x[j-1], x[j]) + bias + V[j-1+q]), q = 0, 1, V[-1] = 0 per
+    clip -- the causal v1.0 time up-sampler as three frame products.  x [B, T, H, W, Cin]; out [B, 2T, H, W, ld] in x's type.
+    wu = (packed [W0 | W2] rows [cout, 18 Cin], fp32 bias or None) and v = V = W1 x [B, T, H, W, ldv] in x's type -- or callables giving
+    them, run only once vt_time_upsample3_supported has said yes (nothing is packed, computed or allocated for a refused launch).
+    ln = (gamma, beta, eps, silu): also n = [SiLU](LayerNorm(out)) where vt_conv_plan fuses it into this launch, into ln_out (a tensor
+    like out, or a callable giving one); elsewhere the launch runs without and the consumer normalises out itself.
+    Returns out, (out, n), or None where the launch is not served (the caller runs the two parity launches of ops.conv)."""
+    if not x.is_cuda or x.dtype not in _DT:      # (as flash_attention_supported: the CPU host-logic tests keep the parity launches)
+        return None
+    lib = L.load()
+    _chk(x, "time_upsample3.x"); _chk(out, "time_upsample3.out")
+    B, T, H, W, Cin = x.shape
+    ld = out.shape[4]
+    assert out.dtype == x.dtype and tuple(out.shape[:4]) == (B, 2 * T, H, W) and ld >= cout, (out.shape, x.shape)
+    assert mix_factor.dtype == torch.float32 and mix_factor.is_cuda
+    g = TUP3_GEOM
+    d = TimeUp3Desc()
+    d.x, d.w, d.y = x.data_ptr(), x.data_ptr(), out.data_ptr()             # (w: a stand-in until the launch is known to be served)
+    d.B, d.Ti, d.Hi, d.Wi, d.Cin = B, T, H, W, Cin
+    d.To, d.Ho, d.Wo, d.Cout = T, H, W, cout
+    d.ldw, d.ldy = g.kt * g.kh * g.kw * Cin, ld
+    d.KT, d.KH, d.KW, d.st, d.sh, d.sw, d.pt, d.ph, d.pw = g.kt, g.kh, g.kw, 1, 1, 1, g.pt, g.ph, g.pw
+    d.tmode = L.VT_TPAD_ZERO
+    d.res_mode, d.res, d.res_tshift, d.Tr, d.ldr, d.mix_factor = L.VT_RES_MIX, x.data_ptr(), 0, T, Cin, mix_factor.data_ptr()
+    d.out_layout, d.dtype, d.out_dtype, d.nbatch = L.VT_NDHWC, _DT[x.dtype], _DT[x.dtype], 1
+    d.yt_mul, d.yt_off = 2, 0
+    if ln is not None:
+        gamma, beta, eps, silu = ln
+        assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() >= cout and beta.numel() >= cout
+        d.ln_gamma, d.ln_beta, d.ln_out = gamma.data_ptr(), beta.data_ptr(), out.data_ptr()    # (ln_out: a placeholder until the plan is known)
+        d.ln_mode, d.ln_keep_y, d.ldn, d.ln_eps = (2 if silu else 1), 1, ld, float(eps)
+        try:
+            fused = conv_plan(d)["ln_fused"]
+        except L.VtError:            # "LayerNorm of an interleaved output is only available fused": this launch cannot take it
+            fused = False
+        if not fused:
+            d.ln_gamma = d.ln_beta = d.ln_out = None
+            d.ln_mode = 0
+            ln = None
+    if not time_upsample3_supported(d):
+        return None
+    w, bias = wu() if callable(wu) else wu
+    _chk(w, "time_upsample3.w")
+    assert w.dtype == x.dtype and tuple(w.shape) == (cout, d.ldw), (w.shape, w.dtype)
+    assert bias is None or (bias.dtype == torch.float32 and bias.numel() >= cout)
+    d.w, d.bias = w.data_ptr(), (bias.data_ptr() if bias is not None else None)
+    v = v() if callable(v) else v
+    _chk(v, "time_upsample3.v")
+    assert v.dtype == x.dtype and tuple(v.shape[:4]) == (B, T, H, W) and v.shape[4] >= cout, (v.shape, x.shape)
+    d.v_ptr, d.ldv = v.data_ptr(), v.shape[4]
+    n = None
+    if ln is not None:
+        n = ln_out() if callable(ln_out) else ln_out
+        if n is None:
+            n = (torch.zeros if ld != cout else torch.empty)(out.shape, dtype=out.dtype, device=x.device)
+        assert n.shape == out.shape and n.dtype == out.dtype and n.is_contiguous()
+        d.ln_out = n.data_ptr()
+    L.check(lib.vt_time_upsample3(C.byref(d), C.c_void_p(d.v_ptr), d.ldv, _stream()), "vt_time_upsample3")
+    if CONV_RECORD is not None:
+        CONV_RECORD.append((d, (x, w, bias, out, mix_factor, n, ln, v), (B * T * H * W, cout, d.ldw)))
+    return out if n is None else (out, n)
+
+
 def _tblock_desc(x, tmode, c=None, caches=None, cache_offset=0):
     d = L.TBlockDesc()
     B, T, H, W, ld = x.shape
@@ -367,6 +450,9 @@ def launch_bytes(d):
         es = 2
         px = d.B * d.T * d.HW
         return px * d.ld * es * (1 + (1 if d.keep_y else 0) + (1 if d.ln_next_mode else 0)) + 2 * d.C * 3 * d.C * es
+    if isinstance(d, TimeUp3Desc):               # x (the mix operand too) and V in, the weights, both frames of every pair (and their LayerNorm) out
+        px = d.B * d.To * d.Ho * d.Wo
+        return px * d.Cin * 2 + d.Cout * d.ldw * 2 + px * d.Cout * 2 * (1 + 2 + (2 if d.ln_mode != 0 else 0))
     es = 2 if d.dtype in (L.VT_BF16, L.VT_F16) else 4
     eo = 4 if d.out_dtype == L.VT_F32 else 2
     nb = max(1, d.nbatch)

@@ -110,6 +110,28 @@ def time_upsample_parity_mix(kdims, early: bool):
     return first + second
 
 
+def time_upsample3_weights(weight: torch.Tensor, part: str):
+    """The causal v1.0 time up-sampler as three frame products (vt_time_upsample3): with x[-1] = 0
+      o[2j] = U[j] + V[j-1],  o[2j+1] = U[j] + V[j],   U[j] = W0 x[j-1] + W2 x[j],  V[j] = W1 x[j]
+    part "u": the k=2 window [W0, W2] over (x[j-1], x[j]); part "v": W1 alone, a per-frame kh x kw convolution.  No tap is summed: every
+    tap is the reference's, rounded once when packed.  weight [Co, Ci, 3, kh, kw] -> [Co, Ci, 2, kh, kw] / [Co, Ci, 1, kh, kw]."""
+    w = weight.detach().to(torch.float32)
+    assert w.dim() == 5 and w.shape[2] == 3 and part in ("u", "v")
+    if part == "u":
+        return torch.stack([w[:, :, 0], w[:, :, 2]], dim=2)
+    return w[:, :, 1:2]
+
+
+def time_upsample3_mix(kdims, part: str):
+    """time_upsample3_weights as a mix table for vt_pack_conv_weight: (3, kh, kw) -> 2 * kh * kw (u) or kh * kw (v) single taps"""
+    kt, kh, kw = kdims
+    assert kt == 3 and part in ("u", "v")
+    s = kh * kw
+    if part == "u":
+        return [[0 * s + i] for i in range(s)] + [[2 * s + i] for i in range(s)]
+    return [[1 * s + i] for i in range(s)]
+
+
 def space_upsample_parity_mix(kdims, py: int, px: int):
     """the tap sums of space_upsample_parity_weights as a mix table: (3, 3) -> 4 output taps (r, c), each (w[r0][c0] + w[r1][c0]) +
     (w[r0][c1] + w[r1][c1]) over its row set and column set -- rows first, then columns, as the host statement sums them"""
@@ -189,18 +211,19 @@ class ConvSite:
     row operand of attention.  `clip_tmode` is the time-pad mode on a whole clip (what the training path runs); chunked passes hand `run`
     their own mode and cache (CausalConv3d / CausalConv1d)."""
 
-    def __init__(self, conv, geom, *, clip_tmode=L.VT_TPAD_ZERO, transform=None, mix=None, pin_native=False):
+    def __init__(self, conv, geom, *, clip_tmode=L.VT_TPAD_ZERO, transform=None, mix=None, pin_native=False, bias=True):
         self.conv, self.geom, self.clip_tmode = conv, geom, clip_tmode
+        self.bias = bias             # False: the site runs without the holder's bias (one of several terms of the holder's convolution)
         self.cin, self.cout = conv.in_channels, conv.out_channels
         self.pack = PackedCache(transform, pin_native, mix)
         self._dgrad = None           # DgradPackCache, made by the first backward
 
     def rows(self, dt, cin_stored):
         """(packed weight rows, fp32 bias) alone, for the launches that are not ops.conv"""
-        return self.pack.get(self.conv.weight, self.conv.bias, dt, cin_stored=cin_stored)
+        return self.pack.get(self.conv.weight, self.conv.bias if self.bias else None, dt, cin_stored=cin_stored)
 
     def run(self, x, dt, *, tmode=L.VT_TPAD_ZERO, cache=None, **kw):
-        w, b = self.pack.get(self.conv.weight, self.conv.bias, dt, cin_stored=x.shape[-1])
+        w, b = self.rows(dt, x.shape[-1])
         return ops.conv(x, w, b, self.geom, cout=self.cout, tmode=tmode, cache=cache, **kw)
 
     def run_clip(self, x, dt, **kw):

@@ -187,6 +187,8 @@ typedef struct vt_conv_desc {
   int32_t To, Ho, Wo, Cout;
   int32_t ldw;              /* row stride of w in elements (>= KT*KH*KW*Cin, multiple of 16 B) */
   int32_t ldy;              /* channel stride of y for NDHWC                                   */
+                            /* (lanes Cout .. ldy-1 of a row, and Cout .. ldn-1 of ln_out, are left unchanged or zero-filled:
+                             *  a caller that zeroes them once may rely on zeros -- tests/test_gpu_arena.py holds every kernel to it) */
   int32_t KT, KH, KW;
   int32_t st, sh, sw;
   int32_t pt, ph, pw;

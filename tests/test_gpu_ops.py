@@ -241,10 +241,8 @@ TBLOCK_CASES = [  # (B, T, H, W), tmode, next norm (None | silu flag), keep_y
 ]
 
 
-@pytest.mark.parametrize("dt", H16, ids=H16_IDS)
-@pytest.mark.parametrize("shape,tmode,nxt,keep", TBLOCK_CASES, ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}" for c in TBLOCK_CASES])
-def test_temporal_block_fused(shape, tmode, nxt, keep, dt):
-    """vt_temporal_block (one launch) vs the unfused operator sequence it replaces, stated in torch on the host"""
+def _tblock_operands(shape, dt):
+    """x, the two packed k=3 weights, their biases, (gamma, beta) of norm1, norm2 and the next block's norm"""
     B, T, H, W = shape
     C_ = 128
     x = _act(B, T, H, W, C_, dt, 1)
@@ -252,6 +250,16 @@ def test_temporal_block_fused(shape, tmode, nxt, keep, dt):
     ws = [pack_conv_weight(torch.randn((C_, C_, 3), generator=g) / math.sqrt(3 * C_), dt, cin_stored=C_).to(DEV) for _ in range(2)]
     bs = [_rand((C_,), torch.float32, 3 + i, 0.1) for i in range(2)]
     norms = [(_rand((C_,), torch.float32, 10 + i, 0.3) + 1.0, _rand((C_,), torch.float32, 20 + i, 0.2)) for i in range(3)]
+    return x, ws, bs, norms
+
+
+@pytest.mark.parametrize("dt", H16, ids=H16_IDS)
+@pytest.mark.parametrize("shape,tmode,nxt,keep", TBLOCK_CASES, ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}" for c in TBLOCK_CASES])
+def test_temporal_block_fused(shape, tmode, nxt, keep, dt):
+    """vt_temporal_block (one launch) vs the unfused operator sequence it replaces, stated in torch on the host"""
+    B, T, H, W = shape
+    C_ = 128
+    x, ws, bs, norms = _tblock_operands(shape, dt)
     next_ln = None if nxt is None else (norms[2][0], norms[2][1], nxt)
     assert ops.temporal_block_supported(x, tmode)
     out = ops.temporal_block(x, ws[0], bs[0], ws[1], bs[1], norms[0], norms[1], tmode=tmode, next_ln=next_ln, keep_y=keep)
@@ -284,11 +292,7 @@ def test_temporal_block_chunked(shape, off, cuts, dt):
     the bits of the same clip run in one launch: the ring rows a chunk restores are the ring rows the previous one had."""
     B, T, H, W = shape
     C_ = 128
-    x = _act(B, T, H, W, C_, dt, 1)
-    g = torch.Generator().manual_seed(2)
-    ws = [pack_conv_weight(torch.randn((C_, C_, 3), generator=g) / math.sqrt(3 * C_), dt, cin_stored=C_).to(DEV) for _ in range(2)]
-    bs = [_rand((C_,), torch.float32, 3 + i, 0.1) for i in range(2)]
-    norms = [(_rand((C_,), torch.float32, 10 + i, 0.3) + 1.0, _rand((C_,), torch.float32, 20 + i, 0.2)) for i in range(3)]
+    x, ws, bs, norms = _tblock_operands(shape, dt)
     nxt = (norms[2][0], norms[2][1], True)
     run = lambda xs, **kw: ops.temporal_block(xs.contiguous(), ws[0], bs[0], ws[1], bs[1], norms[0], norms[1], next_ln=nxt, **kw)
     whole = run(x, tmode=L.VT_TPAD_REPLICATE)
@@ -534,8 +538,9 @@ def _ref_cached(key, fn):
     return val
 
 
-def _check_conv(case, dtype, keep_outputs=None):
-    """one case against the host reference; returns vt_conv_plan of the launch (keep_outputs: a list that receives the device results)"""
+def _conv_operands(case, dtype):
+    """the device operands of one case -> (x, w, w_rows, bias, kw, ln): ops.conv(x, w, bias, geom, cout=cout, **kw) is the launch, w_rows
+    the packed rows the host reference reads (w itself unless dtype is X3), ln = None or (gamma, beta, keep_y)"""
     name, (B, T, H, W), cin, cout, kdims, geom, ex = case
     mode, dtype = dtype, (torch.float32 if dtype == X3 else dtype)      # x3: fp32 tensors, split weight planes
     x = _act(B, T, H, W, cin, dtype, 1)
@@ -562,9 +567,19 @@ def _check_conv(case, dtype, keep_outputs=None):
         kw.update(tmode=L.VT_TPAD_REPLICATE)
     elif ex.get("tmode") == "cache":
         kw.update(tmode=L.VT_TPAD_CACHE, cache=_act(B, geom.pt + 1, H, W, cin, dtype, 5))
+    ln = None
     if "ln" in ex:
-        gam, bet = _rand((cout,), torch.float32, 6, 0.5) + 1.0, _rand((cout,), torch.float32, 7, 0.2)
-        keep = ex["ln"] == "keep"
+        ln = (_rand((cout,), torch.float32, 6, 0.5) + 1.0, _rand((cout,), torch.float32, 7, 0.2), ex["ln"] == "keep")
+    return x, w, w_rows, bias, kw, ln
+
+
+def _check_conv(case, dtype, keep_outputs=None):
+    """one case against the host reference; returns vt_conv_plan of the launch (keep_outputs: a list that receives the device results)"""
+    name, _shape, _cin, cout, _kdims, geom, ex = case
+    mode = dtype
+    x, w, w_rows, bias, kw, ln = _conv_operands(case, dtype)
+    if ln is not None:
+        gam, bet, keep = ln
         ops.CONV_RECORD = []
         out = ops.conv(x, w, bias, geom, cout=cout, ln=(gam, bet, 1e-6, True), ln_keep_y=keep, **kw)
         rec, ops.CONV_RECORD = ops.CONV_RECORD, None
@@ -699,7 +714,7 @@ def test_flash_attention_declines_other_shapes(vt_opts):
     assert not ops.flash_attention_supported(q, torch.zeros((1, 512, 64), dtype=torch.bfloat16, device=DEV))          # switched off
 
 
-@pytest.mark.parametrize("C", [32, 64, 128, 256, 512, 1024])
+@pytest.mark.parametrize("C", [32, 64, 128, 192, 256, 512, 1024])
 @pytest.mark.parametrize("din,dout", [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
                                       (torch.float32, torch.bfloat16), (torch.bfloat16, torch.float32),
                                       (F16, F16), (torch.float32, F16), (F16, torch.float32)])

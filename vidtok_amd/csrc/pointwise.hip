@@ -178,12 +178,13 @@ __global__ __launch_bounds__(kBlock) void layernorm_act_kernel(const TI* __restr
 template <typename TI, typename TO>
 int launch_layernorm(const void* x, long long ldx, void* y, long long ldy, const float* gamma,
                      const float* beta, long long M, int C, float eps, int silu, hipStream_t stream) {
-  // choose lanes-per-position LP (power of two <= 64) and chunks-per-lane R with C == 8*LP*R
+  // choose lanes-per-position LP (power of two <= 64) and chunks-per-lane R with C == 8*LP*R (R = 3 for C = 192 only: 8 lanes x 3 chunks)
   int LP = 0, R = 0;
+  if (C == 192) { LP = 8; R = 3; }
   for (int lp = 64; lp >= 4 && LP == 0; lp >>= 1)
     for (int r = 1; r <= 4; r <<= 1)
       if (C == 8 * lp * r) { LP = lp; R = r; break; }
-  VT_CHECK_ARG(LP != 0, "vt_layernorm_act: unsupported channel count C=%d (need C = 8*LP*R, LP in {4..64}, R in {1,2,4})", C);
+  VT_CHECK_ARG(LP != 0, "vt_layernorm_act: unsupported channel count C=%d (need C = 8*LP*R, LP in {4..64}, R in {1,2,4}, or C = 192)", C);
   const int groups = (kBlock / LP) * ((R == 1) ? 4 : 2);   // positions per workgroup and iteration
   long long blocks = (M + groups - 1) / groups;
   if (blocks > kMaxGrid) blocks = kMaxGrid;
@@ -200,7 +201,7 @@ int launch_layernorm(const void* x, long long ldx, void* y, long long ldy, const
     return VT_OK;                                                                                    \
   }
   VT_LN_CASE(64, 1) VT_LN_CASE(64, 2) VT_LN_CASE(64, 4)
-  VT_LN_CASE(32, 1) VT_LN_CASE(16, 1) VT_LN_CASE(8, 1) VT_LN_CASE(4, 1)
+  VT_LN_CASE(32, 1) VT_LN_CASE(16, 1) VT_LN_CASE(8, 1) VT_LN_CASE(4, 1) VT_LN_CASE(8, 3)
 #undef VT_LN_CASE
   vt_set_error("vt_layernorm_act: no kernel for LP=%d R=%d", LP, R);
   return VT_ERR_UNSUPPORTED;

@@ -238,6 +238,26 @@ int64_t vt_conv_work_bytes(const vt_conv_desc* d);
  *               for full tiles in a 16-bit type), 2 if the 128 x 128 tile runs on its 4-slot ring (option conv_deep: launches with no more
  *               tiles than the device has CUs), else 0 */
 int vt_conv_plan(const vt_conv_desc* d, int32_t* out8);
+/* The form of the implicit-GEMM launch behind a call, without launching (no GPU needed; validates exactly like the call it describes).
+ * The plan above names kernel, tile, epilogue and ring; this is the rest of the same decision -- every choice in it leaves the result
+ * bit-equal, so only this report shows whether a layer keeps its descriptor gather, its skipped taps or its tile order.
+ *   call  0 = vt_conv(d): the partial launch where d->work / d->work_bytes make the split run, else the whole launch
+ *         1 = vt_time_upsample3(d, ..): the paired launch (VT_ERR_ARG where vt_time_upsample3_supported(d) is 0)
+ *         2 = vt_conv_act(d, VT_ACT_RELU)
+ *   out16[0]      kernel, as out8[6] of vt_conv_plan; the launches of kernels 2, 3, 4 report it and zeros
+ *   out16[1]      gather form: 1 = buffer descriptors, 0 = 64-bit pointers (option conv_buf = 0, a tensor of 4 GiB, a cache-mode tile that
+ *                 spans frames)
+ *   out16[2..4]   descriptor extents in bytes of x, the weights and the cache (0 on pointers)
+ *   out16[5]      1 if zero-padded time taps in front of the clip are skipped per tile (option conv_tskip)
+ *   out16[6]      > 0: pixel tiles per frame, tiles walked frames-innermost (option conv_tinner); 0 = pixel order
+ *   out16[7]      1 if full 128 x 128 tiles go through the LDS-transposed epilogue (meaningful on that tile only)
+ *   out16[8]      K steps per tile      out16[9..10]  pixel x channel tiles      out16[11]  grid z (nbatch, or the split planes)
+ *   out16[12]     0 whole launch; split-K partial launch over 1 = the time taps, 2 = the rows of a 3 x 3
+ *   out16[13]     K-step schedule of the instantiation (0 plain loop, 1 / 2 / 5 the scheduled loops of the 8-wave tile)
+ *   out16[14]     dynamic LDS bytes
+ *   out16[15]     the instantiation: tile index (0 = 256 x 32, 1 = 256 x 64, 2 = 256 x 256, 3 = 128 x 128) | tap-walk form << 4 |
+ *                 LDS epilogue of the 8-wave tile (0 none, 1 plain / LayerNorm, 2 paired) << 8 | ring slots << 12 | K bytes per row and step << 16 */
+int vt_conv_launch_form(const vt_conv_desc* d, int32_t call, int64_t* out16);
 /* Measurement aid (scripts/conv_profile.py): vt_conv(d) on the bf16 8-wave 256 x 256 tile (no LayerNorm) with shader-clock
  * stamps at the phase boundaries of K steps 8..11 of workgroup 0: stamps_out (device, 8*4*8 uint64) = [wave][step][stamp] */
 int vt_conv_profile(const vt_conv_desc* d, uint64_t* stamps_out, vt_stream stream);

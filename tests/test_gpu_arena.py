@@ -70,24 +70,22 @@ def _replay_check(entry, family, pre=None):
     elif isinstance(d, tuple):
         REACHED.add(("flash",))
     else:
-        REACHED.add((plan["kernel"], plan["tile"], _lds_epilogue(plan), plan["deep_ring"], plan["launches"] > 1))
+        REACHED.add((plan["kernel"], plan["tile"], _lds_epilogue(plan, d), plan["deep_ring"], plan["launches"] > 1))
     COUNTS[family] += 1
     return plan, ar
 
 
-def _lds_epilogue(plan):
-    """vt_conv_plan reports the LDS epilogue of the 8-wave tile and of conv_in8.  The 128 x 128 tile takes conv_epilogue_lds128 tile by
-    tile (full tiles of an NDHWC output under option conv_ldsepi), which no plan field says -- but a LayerNorm fused on that tile exists
-    only in that epilogue (True), and with the option off no tile takes it (False); None: not known from the plan"""
+def _lds_epilogue(plan, d):
+    """vt_conv_plan reports the LDS epilogue of the 8-wave tile and of conv_in8; for the 128 x 128 tile, whose full tiles take
+    conv_epilogue_lds128, vt_conv_launch_form does"""
     if plan["kernel"] != "igemm" or plan["tile"] != (128, 128):
         return plan["lds_epilogue"]
-    if plan["ln_fused"]:
-        return True
-    return False if L.get_option("conv_ldsepi") == 0 else None
+    return bool(ops.conv_launch_form(d)["lds_epi"])
 
 
-def _conv_case(case, dtype, family):
-    """the launch of one case of a table of tests/test_gpu_ops.py, plain and relocated -> (plan, arena)"""
+def _conv_case(case, dtype, family, forms=None):
+    """the launch of one case of a table of tests/test_gpu_ops.py, plain and relocated -> (plan, arena); forms: a list that receives
+    vt_conv_launch_form of the plain launch"""
     _name, _shape, _cin, cout, _kdims, geom, _ex = case
     x, w, _rows, bias, kw, ln = T._conv_operands(case, dtype)
     with recording() as rec:
@@ -97,6 +95,8 @@ def _conv_case(case, dtype, family):
             ops.conv(x, w, bias, geom, cout=cout, **kw)
     torch.cuda.synchronize()
     assert len(rec) == 1
+    if forms is not None:
+        forms.append(ops.conv_launch_form(rec[0][0]))
     return _replay_check(rec[0], family)
 
 
@@ -113,7 +113,15 @@ assert len(FOUR_ARITHMETICS) == 3
 @pytest.mark.parametrize("case,dtype", _params(T.CONV_CASES, [BF16, F32]) + _params(FOUR_ARITHMETICS, [X3, F16]))
 def test_conv_cases(case, dtype, buf, vt_opts):
     vt_opts(conv_buf=buf)
-    _conv_case(case, dtype, "igemm tables (CONV_CASES)")
+    forms = []
+    plan, _ = _conv_case(case, dtype, "igemm tables (CONV_CASES)", forms=forms)
+    # descriptors unless switched off -- or in cache mode, where they need the tap walk (Cin a multiple of the K step) and frames of whole tiles
+    if plan["kernel"] == "igemm":
+        (_b, Tt, H, W), cin, geom = case[1], case[2], case[5]
+        _to, Ho, Wo = geom.out_dims(Tt, H, W)
+        step = 64 if dtype in T.H16 else 16 if dtype is X3 and plan["tile"] == (256, 256) else 32
+        desc = bool(buf) and (case[6].get("tmode") != "cache" or (cin % step == 0 and (Ho * Wo) % plan["tile"][0] == 0))
+        assert forms[0]["gather"] == ("desc" if desc else "ptr") and (forms[0]["x_bytes"] > 0) == desc, forms[0]
 
 
 @pytest.mark.parametrize("case,dtype", _params(T.BIG256, [BF16, F32]))

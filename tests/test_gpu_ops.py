@@ -370,8 +370,10 @@ def test_conv_pointer_gather(case, dtype, tile, vt_opts):
     vt_opts(conv_buf=0)
     if tile:
         vt_opts(conv_tile=tile)
-    plan = _check_conv(case, dtype)
+    forms = []
+    plan = _check_conv(case, dtype, forms=forms)
     assert not tile or plan["tile"] == (256, 256)
+    assert forms[0]["gather"] == "ptr" and forms[0]["x_bytes"] == 0, forms[0]
 
 
 SCHED_CASES = [c for c in BIG256 if c[0] in ("nin_1x1_128_256", "nin_1x1_64_256_one_kstep", "temporal_k3_512", "conv3d_333_256", "v11_cache_1d", "nc_conv1d_sym_512",
@@ -400,8 +402,12 @@ def test_conv_cache_mode_gather_forms(case, gather, dtype, vt_opts):
     vt_opts(conv_buf=(0 if gather == "pointers" else 1))
     if case[3] % 256 == 0:
         vt_opts(conv_tile=256)
-    plan = _check_conv(case, dtype)
+    forms = []
+    plan = _check_conv(case, dtype, forms=forms)
     assert plan["tile"][0] in (128, 256)
+    # every case here has frames of whole tiles (256 or 1 024 pixels), so only the option decides the form
+    form, desc = forms[0], gather == "descriptors"
+    assert form["kernel"] == "igemm" and form["gather"] == ("desc" if desc else "ptr") and (form["c_bytes"] > 0) == desc, form
 
 
 # The 128 x 128 tile has two rings: two slots (two workgroups per CU cover each other's DMA latency) and, for launches with
@@ -573,8 +579,9 @@ def _conv_operands(case, dtype):
     return x, w, w_rows, bias, kw, ln
 
 
-def _check_conv(case, dtype, keep_outputs=None):
-    """one case against the host reference; returns vt_conv_plan of the launch (keep_outputs: a list that receives the device results)"""
+def _check_conv(case, dtype, keep_outputs=None, forms=None):
+    """one case against the host reference; returns vt_conv_plan of the launch (keep_outputs: a list that receives the device results;
+    forms: a list that receives vt_conv_launch_form of the launch)"""
     name, _shape, _cin, cout, _kdims, geom, ex = case
     mode = dtype
     x, w, w_rows, bias, kw, ln = _conv_operands(case, dtype)
@@ -594,6 +601,8 @@ def _check_conv(case, dtype, keep_outputs=None):
             e = rel_err(o, r)
             # the normalised output amplifies the bf16 rounding of y when the library normalises the stored y
             assert e < 2 * TOL[mode], f"{name} {mode}: rel_err={e}"
+        if forms is not None:
+            forms.append(ops.conv_launch_form(rec[0][0]))
         return ops.conv_plan(rec[0][0])
     ops.CONV_RECORD = []
     y = ops.conv(x, w, bias, geom, cout=cout, **kw)
@@ -607,6 +616,8 @@ def _check_conv(case, dtype, keep_outputs=None):
     e = rel_err(y, yr)
     print(f"{name} {mode}: rel_err={e:.3e}")
     assert e < TOL[mode], f"{name} {mode}: rel_err={e}"
+    if forms is not None:
+        forms.append(ops.conv_launch_form(rec[0][0]))
     return ops.conv_plan(rec[0][0])
 
 
@@ -917,15 +928,44 @@ TSKIP_CASES = [
 def test_conv_time_tap_skip_is_bit_exact(case, dtype, tile, vt_opts):
     if tile == 256 and case[3] % 256 != 0:
         pytest.skip("256 tile needs Cout % 256")
-    outs = {}
+    outs, forms = {}, {}
     for skip in (1, 0):
         vt_opts(conv_tskip=skip, conv_tile=tile, conv_ws=0)
-        keep = []
-        _check_conv(case, dtype, keep_outputs=keep)
-        outs[skip] = keep
+        keep, form = [], []
+        _check_conv(case, dtype, keep_outputs=keep, forms=form)
+        outs[skip], forms[skip] = keep, form[0]
+    # the comparison below compares two walks only if the skip engaged: every case qualifies (frames of 256 or 1 024 pixels = whole tiles,
+    # the tap walk on descriptors, zero padding in front) but for a split-K launch, whose planes walk one time tap each
+    assert forms[0]["kernel"] == "igemm" and forms[0]["tskip"] == 0, forms[0]
+    assert forms[1]["tskip"] == (0 if forms[1]["ksplit"] else 1), forms[1]
     assert len(outs[1]) == len(outs[0]) >= 1
     for a, b in zip(outs[1], outs[0]):
         assert torch.equal(a, b), f"{case[0]}: the skipped walk differs from the full one"
+
+
+# Frames-innermost tile order (option conv_tinner, default on): a temporal convolution whose frames are whole pixel tiles walks its tiles
+# as (clip, tile of the frame, frame), so that the frames a tile reads were written to the cache right before it.  Only the order of the
+# tiles changes, so the result must be the SAME BITS as in pixel order -- on both tile heights (two tiles per frame on the 128-pixel
+# tile, one on the 256-pixel tile), with two clips so that the clip index of the remapped tile number counts.
+TINNER_CASES = [
+    ("tinner_k3_64_128", (2, 3, 16, 16), 64, 128, (3,), ConvGeom(kt=3, pt=2), {}, 0, 2),
+    ("tinner_k3_64_256", (2, 3, 16, 16), 64, 256, (3,), ConvGeom(kt=3, pt=2), {}, 256, 1),
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("case", TINNER_CASES, ids=[c[0] for c in TINNER_CASES])
+def test_conv_frames_innermost_is_bit_exact(case, dtype, vt_opts):
+    tile, hw_tiles = case[7:]
+    outs, forms = {}, {}
+    for inner in (1, 0):
+        vt_opts(conv_tinner=inner, conv_tile=tile)
+        keep, form = [], []
+        plan = _check_conv(case[:7], dtype, keep_outputs=keep, forms=form)
+        assert plan["kernel"] == "igemm" and plan["tile"] == ((256, 256) if tile else (128, 128))
+        outs[inner], forms[inner] = keep, form[0]
+    assert forms[1]["hw_tiles"] == hw_tiles and forms[0]["hw_tiles"] == 0, forms
+    assert len(outs[1]) == len(outs[0]) == 1 and torch.equal(outs[1][0], outs[0][0]), f"{case[0]}: the frames-innermost order differs from pixel order"
 
 
 def test_conv_split_k_does_not_depend_on_the_batch(vt_opts):

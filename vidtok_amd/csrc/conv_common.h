@@ -63,12 +63,12 @@ struct ConvArgs {
   long long yt_step, yt_base;    // (yt_mul - 1) * Ho*Wo and yt_off * Ho*Wo rows
   int ys_mul, ys_oh, ys_ow;      // 2: computed pixel (ho, wo) is output pixel (2 ho + ys_oh, 2 wo + ys_ow) of a 2Ho x 2Wo frame
   int lds_epi;                 // 128 x 128 tile: epilogue transposed through the LDS (coalesced rows)
-  int hw_tiles;                // > 0: pixel tiles per frame, tile order (b, hw tile, t) -- see launch_variant
+  int hw_tiles;                // > 0: pixel tiles per frame, tile order (b, hw tile, t) -- see igemm_launch_form (conv_select.h)
   unsigned x_bytes, w_bytes;   // BUF path: descriptor extents (0 = tensors too large, use pointers)
   unsigned c_bytes;            // BUF path in cache mode: extent of the cache tensor [B][ncache][Hi][Wi][Cin]
   long long xs_z, ws_z, ys_z, rs_z;
   int in8_rt, in8_ct, in8_ctl2, in8_segs;   // conv_in8_kernel: tile = in8_rt rows x in8_ct (= 2^in8_ctl2) columns; 64-pixel segments per patch row
-  int tskip;                   // 1: zero-padded time taps in front of the clip are skipped per tile (tile inside one output frame, tmode ZERO; launch_variant)
+  int tskip;                   // 1: zero-padded time taps in front of the clip are skipped per tile (tile inside one output frame, tmode ZERO; igemm_launch_form)
   int ksplit;                  // split-K: blockIdx.z = tap plane, the walk covers that plane only; 1: planes = kt, 2: planes = kh (KT = 1)
   unsigned plane_bytes;        //      bytes of one tap plane in a weight row (KH * KW * Cin, or KW * Cin, elements)
   int nt_store;                // 1: the LDS epilogues write y / LayerNorm(y) with streaming (nt) stores (outputs of at least conv_nt_mb MiB)

@@ -47,12 +47,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 // the per-arithmetic translation unit of an implicit-GEMM launch
-int launch_igemm(int dtype, bool out_f32, const ConvArgs& a, const IgemmVariant& v, int nbatch, void* stream) {
+int launch_igemm(int dtype, bool out_f32, const IgemmLaunch& l, void* stream) {
   switch (dtype) {
-    case VT_F32: return vt_igemm_dispatch_f32(&a, &v, nbatch, stream);
-    case VT_BF16X3: return vt_igemm_dispatch_x3(&a, &v, nbatch, stream);
-    case VT_F16: return vt_igemm_dispatch_f16(&a, &v, nbatch, out_f32 ? 1 : 0, stream);
-    default: return vt_igemm_dispatch_bf16(&a, &v, nbatch, out_f32 ? 1 : 0, stream);
+    case VT_F32: return vt_igemm_dispatch_f32(&l, stream);
+    case VT_BF16X3: return vt_igemm_dispatch_x3(&l, stream);
+    case VT_F16: return vt_igemm_dispatch_f16(&l, out_f32 ? 1 : 0, stream);
+    default: return vt_igemm_dispatch_bf16(&l, out_f32 ? 1 : 0, stream);
   }
 }
 
@@ -64,29 +64,46 @@ bool splitk_runs(const ConvPlan& p, const ConvArgs& a, const vt_conv_desc* d, bo
   return !sized || (d->work_bytes >= (int64_t)p.splitk_planes * a.M * a.Cout * 4 && (reinterpret_cast<uintptr_t>(d->work) & 15) == 0);
 }
 
-int launch_splitk(const vt_conv_desc* d, const ConvArgs& a_in, const ConvPlan& p, hipStream_t stream) {
+// the plan's partial launch (p.part: conv_decide built its arguments), then the reduction over the planes into a's y
+int launch_splitk(const vt_conv_desc* d, const ConvArgs& a, const ConvPlan& p, hipStream_t stream) {
   const int planes = p.splitk_planes;
-  ConvArgs a = a_in;
-  a.ksplit = a.KT == 3 ? 1 : 2;
-  a.plane_bytes = (unsigned)((a.KT == 3 ? a.KH * a.KW : a.KW) * a.Cin * 2);
-  a.y = reinterpret_cast<char*>(d->work);
-  a.bias = nullptr;
-  a.res = nullptr; a.res_mode = VT_RES_NONE;
-  a.ln_mode = 0;
-  a.xs_z = 0; a.ws_z = 0; a.rs_z = 0;
-  a.ys_z = (long long)a.M * a.ldy;
-  int rc = launch_igemm(d->dtype, true, a, p.split, planes, stream);
+  if (p.part_rc != VT_OK) return p.part_rc;       // conv_decide found no form for the partial launch, and said why
+  int rc = launch_igemm(d->dtype, true, p.part, stream);
   if (rc != VT_OK) return rc;
   const long long n8 = (long long)a.M * (a.Cout / 8);
   const unsigned grid = (unsigned)std::min<long long>((n8 + 255) / 256, 4096);
-  const void* res = a_in.res_mode == VT_RES_ADD ? a_in.res : nullptr;
+  const void* res = a.res_mode == VT_RES_ADD ? a.res : nullptr;
   if (d->dtype == VT_F16)
-    hipLaunchKernelGGL(splitk_reduce_kernel<f16_t>, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float*>(d->work), planes, (long long)a.M, a.Cout, a_in.bias,
-                       reinterpret_cast<const f16_t*>(res), reinterpret_cast<f16_t*>(a_in.y));
+    hipLaunchKernelGGL(splitk_reduce_kernel<f16_t>, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float*>(d->work), planes, (long long)a.M, a.Cout, a.bias,
+                       reinterpret_cast<const f16_t*>(res), reinterpret_cast<f16_t*>(a.y));
   else
-    hipLaunchKernelGGL(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float*>(d->work), planes, (long long)a.M, a.Cout, a_in.bias,
-                       reinterpret_cast<const bf16_t*>(res), reinterpret_cast<bf16_t*>(a_in.y));
+    hipLaunchKernelGGL(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float*>(d->work), planes, (long long)a.M, a.Cout, a.bias,
+                       reinterpret_cast<const bf16_t*>(res), reinterpret_cast<bf16_t*>(a.y));
   VT_CHECK_LAUNCH();
+  return VT_OK;
+}
+
+// vt_time_upsample3's decision: the parity descriptor's plan, the serving rule, the form of the paired launch (l.a still without V)
+int tup3_decide(const vt_conv_desc* u, IgemmLaunch& l) {
+  ConvArgs a;
+  ConvPlan p;
+  const int rc = conv_decide(u, a, p);
+  if (rc != VT_OK) return rc;
+  VT_CHECK_ARG(tup3_eligible(u, a, p), "vt_time_upsample3: descriptor not covered (ask vt_time_upsample3_supported; the parity launches of vt_conv serve it)");
+  const IgemmVariant pair = {TILE_256x256, true, 2, 2, kRowBytes};
+  return igemm_launch_form(l, a, pair, 1, u->dtype, u->out_dtype);
+}
+
+// vt_conv_act's decision: vt_conv's descriptor checks with the activation's tile rule, then what the ReLU instantiations cover
+int conv_act_decide(const vt_conv_desc* d, int32_t act, ConvArgs& a, ConvPlan& p) {
+  VT_CHECK_ARG(act == VT_ACT_RELU, "vt_conv_act: act %d (VT_ACT_RELU = %d is the one activation)", act, VT_ACT_RELU);
+  const int rc = conv_decide(d, a, p, nullptr, act);
+  if (rc != VT_OK) return rc;
+  VT_CHECK_ARG(d->dtype != VT_BF16X3 && d->out_dtype == d->dtype, "vt_conv_act: fp32, bf16 or fp16 arithmetic with results in the same type");
+  VT_CHECK_ARG(d->out_layout == VT_NDHWC && d->res_mode == VT_RES_NONE && d->ln_mode == 0 && p.nbatch == 1 && a.yt_mul == 1 && a.ys_mul == 1,
+               "vt_conv_act: NDHWC output without residual, LayerNorm, batching or interleave");
+  VT_CHECK_ARG(p.whole.v.tile == TILE_256x64 || p.whole.v.fast, "vt_conv_act: Cout=%d needs Cin a multiple of %d (got %d)", a.Cout,
+               kRowBytes / (vt_is_h16(d->dtype) ? 2 : 4), a.Cin);
   return VT_OK;
 }
 
@@ -120,12 +137,13 @@ extern "C" int vt_conv_plan(const vt_conv_desc* d, int32_t* out8) {
       out8[7] = 1;
       break;
     case CONV_IGEMM: {
-      const TileShape& t = kTileShapes[p.igemm.tile];
+      const IgemmVariant& v = p.whole.v;
+      const TileShape& t = kTileShapes[v.tile];
       out8[0] = t.bm(); out8[1] = t.bn(); out8[2] = t.waves();
       out8[3] = (int32_t)((long long)((a.M + t.bm() - 1) / t.bm()) * ((a.Cout + t.bn() - 1) / t.bn()) * p.nbatch);
       if (d->ln_mode != 0 && !p.ln_fused) out8[5] += 1;     // vt_layernorm_act behind the convolution
       if (splitk_runs(p, a, d, false)) out8[5] += 1;        // partial launch + reduction
-      out8[7] = p.igemm.tile == TILE_256x256 ? (p.igemm.ln256 ? 1 : 0) : (p.igemm.stages == 4 ? 2 : 0);
+      out8[7] = v.tile == TILE_256x256 ? (v.ln256 ? 1 : 0) : (v.stages == 4 ? 2 : 0);
       break;
     }
   }
@@ -140,12 +158,11 @@ extern "C" int vt_conv_profile(const vt_conv_desc* d, uint64_t* stamps_out, vt_s
   ConvPlan p;
   const int rc = conv_decide(d, a, p, reinterpret_cast<unsigned long long*>(stamps_out));
   if (rc != VT_OK) return rc;
-  a.prof_mode = vt_opt(OPT_WS_PROF_MODE);
   if (p.kernel == CONV_WS2) return vt_ws2_launch(&a, d->dtype, stream_);       // stamps [wave][16]: conv_ws2.hip iterations 8, 9 of workgroup 0 (8 waves; bf16 only)
   VT_CHECK_ARG(p.kernel == CONV_IGEMM && ((d->dtype == VT_BF16 && d->out_dtype == VT_BF16) || d->dtype == VT_BF16X3) && d->ln_mode == 0 &&
-                   p.igemm.tile == TILE_256x256,
+                   p.whole.v.tile == TILE_256x256,
                "vt_conv_profile: bf16 / split-bf16 launches on the 256 x 256 tile without LayerNorm, or on the weight-stationary kernel");
-  return launch_igemm(d->dtype, false, a, p.igemm, p.nbatch, stream_);
+  return launch_igemm(d->dtype, false, p.whole, stream_);
 }
 
 extern "C" int64_t vt_conv_work_bytes(const vt_conv_desc* d) {
@@ -167,7 +184,7 @@ extern "C" int vt_conv(const vt_conv_desc* d, vt_stream stream_) {
     case CONV_IGEMM: break;
   }
   rc = splitk_runs(p, a, d, true) ? launch_splitk(d, a, p, reinterpret_cast<hipStream_t>(stream_))
-                                  : launch_igemm(d->dtype, d->out_dtype == VT_F32, a, p.igemm, p.nbatch, stream_);
+                                  : launch_igemm(d->dtype, d->out_dtype == VT_F32, p.whole, stream_);
   if (rc != VT_OK || d->ln_mode == 0 || p.ln_fused) return rc;
   // not fusable here: the same contract in two launches
   return vt_layernorm_act(d->y, d->out_dtype, d->ldy, d->ln_out, d->out_dtype, d->ldn, d->ln_gamma, d->ln_beta, a.M, d->Cout,
@@ -185,29 +202,57 @@ extern "C" int vt_time_upsample3_supported(const vt_conv_desc* u) {
 }
 
 extern "C" int vt_time_upsample3(const vt_conv_desc* u, const void* v, int32_t ldv, vt_stream stream_) {
-  ConvArgs a;
-  ConvPlan p;
-  const int rc = conv_decide(u, a, p);
+  IgemmLaunch l;
+  const int rc = tup3_decide(u, l);
   if (rc != VT_OK) return rc;
-  VT_CHECK_ARG(tup3_eligible(u, a, p), "vt_time_upsample3: descriptor not covered (ask vt_time_upsample3_supported; the parity launches of vt_conv serve it)");
   VT_CHECK_ARG(v != nullptr && (reinterpret_cast<uintptr_t>(v) & 15) == 0 && ldv >= u->Cout && ldv % 8 == 0,
                "vt_time_upsample3: v must be 16-byte aligned with ldv = %d >= Cout and a multiple of 8", ldv);
-  a.pair_v = reinterpret_cast<const char*>(v);
-  a.ldv = ldv;
-  const IgemmVariant pair = {TILE_256x256, true, 2, 2, kRowBytes};
-  return launch_igemm(u->dtype, false, a, pair, 1, stream_);
+  l.a.pair_v = reinterpret_cast<const char*>(v);
+  l.a.ldv = ldv;
+  return launch_igemm(u->dtype, false, l, stream_);
 }
 
 // vt_conv with a ReLU epilogue (VGG16's conv + ReLU pairs, LPIPS): the same descriptor checks, then the ACT = VT_ACT_RELU instantiations of
 // conv_igemm_act.hip -- never the weight-stationary, conv_in8, narrow or split-K kernels, whose epilogues have no activation
 extern "C" int vt_conv_act(const vt_conv_desc* d, int32_t act, vt_stream stream_) {
-  VT_CHECK_ARG(act == VT_ACT_RELU, "vt_conv_act: act %d (VT_ACT_RELU = %d is the one activation)", act, VT_ACT_RELU);
   ConvArgs a;
   ConvPlan p;
-  const int rc = conv_decide(d, a, p, nullptr, act);
+  const int rc = conv_act_decide(d, act, a, p);
   if (rc != VT_OK) return rc;
-  VT_CHECK_ARG(d->dtype != VT_BF16X3 && d->out_dtype == d->dtype, "vt_conv_act: fp32, bf16 or fp16 arithmetic with results in the same type");
-  VT_CHECK_ARG(d->out_layout == VT_NDHWC && d->res_mode == VT_RES_NONE && d->ln_mode == 0 && p.nbatch == 1 && a.yt_mul == 1 && a.ys_mul == 1,
-               "vt_conv_act: NDHWC output without residual, LayerNorm, batching or interleave");
-  return vt_igemm_dispatch_relu(&a, &p.igemm, d->dtype, stream_);
+  return vt_igemm_dispatch_relu(&p.whole, d->dtype, stream_);
+}
+
+// the form of the implicit-GEMM launch behind vt_conv (call 0), vt_time_upsample3 (1) or vt_conv_act with ReLU (2), as numbers
+// (out16: include/vidtok_amd.h); the other kernels report themselves and zeros
+extern "C" int vt_conv_launch_form(const vt_conv_desc* d, int32_t call, int64_t* out16) {
+  VT_CHECK_ARG(out16 != nullptr && call >= 0 && call <= 2, "vt_conv_launch_form: null output, or call %d outside 0 .. 2", call);
+  ConvArgs a;
+  ConvPlan p;
+  IgemmLaunch pair;
+  const IgemmLaunch* l = &p.whole;
+  int rc;
+  if (call == 1) {
+    rc = tup3_decide(d, pair);
+    l = &pair;
+  } else if (call == 2) {
+    rc = conv_act_decide(d, VT_ACT_RELU, a, p);
+  } else {
+    rc = conv_decide(d, a, p);
+    if (rc == VT_OK && splitk_runs(p, a, d, true)) {
+      l = &p.part;
+      rc = p.part_rc;
+    }
+  }
+  if (rc != VT_OK) return rc;
+  std::fill(out16, out16 + 16, (int64_t)0);
+  if (call != 1 && p.kernel != CONV_IGEMM) {
+    out16[0] = p.kernel;
+    return VT_OK;
+  }
+  const ConvArgs& f = l->a;
+  const IgemmVariant& v = l->v;
+  const int64_t out[16] = {CONV_IGEMM, l->buf ? 1 : 0, f.x_bytes, f.w_bytes, f.c_bytes, f.tskip, f.hw_tiles, f.lds_epi, f.nsteps, f.m_tiles, f.n_tiles,
+                           l->grid_z, f.ksplit, l->sched, l->lds_bytes, (int)v.tile | ((v.fast ? 1 : 0) << 4) | (v.ln256 << 8) | (v.stages << 12) | (v.rowb << 16)};
+  std::copy(out, out + 16, out16);
+  return VT_OK;
 }

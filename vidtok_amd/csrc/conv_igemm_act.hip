@@ -10,33 +10,32 @@
 namespace {
 
 template <typename MT>
-int dispatch_relu(const ConvArgs& a, const IgemmVariant& v, hipStream_t stream) {
-  constexpr int BK = kRowBytes / (int)sizeof(MT);
+int dispatch_relu(const IgemmLaunch& l, hipStream_t stream) {
+  const IgemmVariant& v = l.v;
   constexpr int R = VT_ACT_RELU;
   VT_CHECK_VARIANT(v.stages == 2 && v.rowb == kRowBytes);
   if (v.tile == TILE_256x64 && v.ln256 == 0) {
-    if (v.fast) return launch_tile<MT, MT, TILE_256x64, true, 0, 2, kRowBytes, R>(a, 1, stream);
-    return launch_tile<MT, MT, TILE_256x64, false, 0, 2, kRowBytes, R>(a, 1, stream);
+    if (v.fast) return launch_variant<MT, MT, TILE_256x64, true, 0, 2, kRowBytes, R>(l, stream);
+    return launch_variant<MT, MT, TILE_256x64, false, 0, 2, kRowBytes, R>(l, stream);
   }
-  VT_CHECK_ARG(v.fast, "vt_conv_act: Cout=%d needs Cin a multiple of %d (got %d)", a.Cout, BK, a.Cin);
+  VT_CHECK_VARIANT(v.fast);        // vt_conv_act refuses the general gather beyond Cout = 64 (conv_act_decide, conv_igemm.hip)
   if (v.tile == TILE_256x256) {
     if constexpr (is_h16<MT>::value) {
-      if (v.ln256) return launch_tile<MT, MT, TILE_256x256, true, 1, 2, kRowBytes, R>(a, 1, stream);
+      if (v.ln256) return launch_variant<MT, MT, TILE_256x256, true, 1, 2, kRowBytes, R>(l, stream);
     }
     VT_CHECK_VARIANT(v.ln256 == 0);
-    return launch_tile<MT, MT, TILE_256x256, true, 0, 2, kRowBytes, R>(a, 1, stream);
+    return launch_variant<MT, MT, TILE_256x256, true, 0, 2, kRowBytes, R>(l, stream);
   }
   VT_CHECK_VARIANT(v.tile == TILE_128x128 && v.ln256 == 0);
-  return launch_tile<MT, MT, TILE_128x128, true, 0, 2, kRowBytes, R>(a, 1, stream);
+  return launch_variant<MT, MT, TILE_128x128, true, 0, 2, kRowBytes, R>(l, stream);
 }
 
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int vt_igemm_dispatch_relu(const void* args, const void* variant, int dtype, void* stream) {
-  const ConvArgs& a = *reinterpret_cast<const ConvArgs*>(args);
-  const IgemmVariant& v = *reinterpret_cast<const IgemmVariant*>(variant);
+extern "C" __attribute__((visibility("hidden"))) int vt_igemm_dispatch_relu(const void* launch, int dtype, void* stream) {
+  const IgemmLaunch& l = *reinterpret_cast<const IgemmLaunch*>(launch);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VT_F32) return dispatch_relu<float>(a, v, s);
-  if (dtype == VT_F16) return dispatch_relu<f16_t>(a, v, s);
-  return dispatch_relu<bf16_t>(a, v, s);
+  if (dtype == VT_F32) return dispatch_relu<float>(l, s);
+  if (dtype == VT_F16) return dispatch_relu<f16_t>(l, s);
+  return dispatch_relu<bf16_t>(l, s);
 }

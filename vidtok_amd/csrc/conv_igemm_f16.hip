@@ -3,9 +3,8 @@
 // attention scores, split-K partials).
 #include "conv_igemm_kernel.h"
 
-extern "C" __attribute__((visibility("hidden"))) int vt_igemm_dispatch_f16(const void* args, const void* variant, int nbatch, int out_f32, void* stream) {
-  const ConvArgs& a = *reinterpret_cast<const ConvArgs*>(args);
-  const IgemmVariant& v = *reinterpret_cast<const IgemmVariant*>(variant);
-  return out_f32 ? dispatch_tile<f16_t, float>(a, v, nbatch, reinterpret_cast<hipStream_t>(stream))
-                 : dispatch_tile<f16_t, f16_t>(a, v, nbatch, reinterpret_cast<hipStream_t>(stream));
+extern "C" __attribute__((visibility("hidden"))) int vt_igemm_dispatch_f16(const void* launch, int out_f32, void* stream) {
+  const IgemmLaunch& l = *reinterpret_cast<const IgemmLaunch*>(launch);
+  return out_f32 ? dispatch_tile<f16_t, float>(l, reinterpret_cast<hipStream_t>(stream))
+                 : dispatch_tile<f16_t, f16_t>(l, reinterpret_cast<hipStream_t>(stream));
 }

@@ -27,7 +27,7 @@
 //     (conv_epilogue_lds128);
 //   * XCD-aware tile order: consecutive tiles of one XCD are neighbouring pixel tiles of the same
 //     channel tile, so halo rows and the weight slab are shared in that XCD's L2; temporal convs walk
-//     the frames innermost (launch_variant).
+//     the frames innermost (igemm_launch_form, conv_select.h).
 //
 // Measured dead ends (kept out of the code): register-staged operand tiles
 // (ds_write_b128 pass: 627 vs 440 TFLOP/s aggregate), a 4-stage ring of 64-B rows (no gain), 256x128 tiles
@@ -677,7 +677,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_igemm_glds_ker
   // against extent 0 (every lane out of range: zeros into a slot nobody reads again, no memory traffic), so
   // the K loop has no branch around any piece and ONE straight-line body
   unsigned ext_x = BUF ? p.x_bytes : 0u, ext_w = BUF ? p.w_bytes : 0u;
-  // BUF in cache mode (v1.1 chunks after the first): a tile lies in ONE output frame (launch_variant checks), so a time tap
+  // BUF in cache mode (v1.1 chunks after the first): a tile lies in ONE output frame (igemm_launch_form checks), so a time tap
   // reads either the cache or x for all of its rows -- the descriptor of the activation pieces is switched per tap
   const MT* x_cur = xg;
   if constexpr (PROF) {            // measurement (option ws_prof_mode): bit 0 / bit 1 = activation / weight pieces become zero fills (no memory traffic)
@@ -808,7 +808,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_igemm_glds_ker
   // (split-K: the walk starts at my tap plane -- kt = z, or kh = z for a convolution without time taps -- and nsteps ends it there)
   int q_step = 0, q_cc = 0, q_kt = p.ksplit == 1 ? (int)blockIdx.z : 0, q_kh = p.ksplit == 2 ? (int)blockIdx.z : 0, q_kw = 0;
   // Causal zero padding (tmode ZERO, the v1.0 models): the time taps in front of the clip multiply zeros.  Where a tile lies
-  // inside ONE output frame (p.tskip: launch_variant checks) those taps are the same for all of its rows, so its K walk simply
+  // inside ONE output frame (p.tskip: igemm_launch_form checks) those taps are the same for all of its rows, so its K walk simply
   // starts at the first tap plane that reads a frame of the clip -- kt0 = -(to * st - pt) for the first frames, 0 elsewhere --
   // and is that many planes shorter: a third / two thirds of the K steps of frames 1 / 0 of a 3-tap convolution, 3 of the 3 T
   // tap planes of a clip (20 % at the T = 5 levels).  The fp32 sum of an output is unchanged (the skipped products are exact
@@ -1460,93 +1460,39 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_igemm_glds_ker
 #endif
 }
 
-template <typename MT, typename TOut, int WAVES_M, int WAVES_N, int TM, int TN, bool FAST, int LN256 = 0, int STAGES = 2, int ROWB = kRowBytes, int ACT = 0>
-int launch_variant(const ConvArgs& a_in, int nbatch, hipStream_t stream) {
-  constexpr int BM = WAVES_M * TM * 32;
-  constexpr int BN = WAVES_N * TN * 32;
-  constexpr int BK = ROWB / (int)sizeof(MT);
-  constexpr int THREADS = 64 * WAVES_M * WAVES_N;
-  constexpr int LDS = STAGES * (BM + BN) * ROWB;
-  ConvArgs a = a_in;
-  a.m_tiles = (a.M + BM - 1) / BM;
-  a.n_tiles = (a.Cout + BN - 1) / BN;
-  a.nsteps = FAST ? a.ntaps * (a.Cin / BK) : (a.K + BK - 1) / BK;
-  if (a.ksplit) {
-    VT_CHECK_ARG(FAST, "vt_conv: split-K needs the tap-walk form");
-    a.nsteps = (a.ksplit == 1 ? a.KH * a.KW : a.KW) * (a.Cin / BK);
-  }
-  // Temporal taps: in pixel order (b,t,h,w) the frames t-1, t-2 a tile reads were last touched one whole frame of
-  // tiles earlier -- far beyond the 4 MiB L2 of its XCD -- so every kt tap came from the fabric again (the k3
-  // temporal conv of the widest level moved 3x its input).  Walking the tiles as (b, hw tile, t) puts the
-  // producers of those lines right before their consumer on the same XCD (xcd_remap keeps the sequence
-  // contiguous): 298 -> 340 TFLOP/s on that layer, +3 % on the 27-tap up-sampler conv (same-run A/B).
-  constexpr int kOctAlign = 16 / (int)sizeof(TOut) > 4 ? 8 : 4;   // elements per 16 bytes, at least a quad
-  a.lds_epi = (vt_opt(OPT_CONV_LDSEPI) != 0 && a.out_layout == VT_NDHWC && a.ldy % kOctAlign == 0 &&
-               (a.res_mode == VT_RES_NONE || a.ldr % kOctAlign == 0) && (a.ln_mode == 0 || a.ldn % kOctAlign == 0)) ? 1 : 0;
-  a.hw_tiles = 0;
-  if (conv_tinner() && a.KT > 1 && a.To > 1 && ((long long)a.Ho * a.Wo) % BM == 0) a.hw_tiles = (int)(((long long)a.Ho * a.Wo) / BM);
-  // descriptor gather needs the tensors under 4 GiB (minus the out-of-range marker)
-  const unsigned long long xb = (unsigned long long)a.B * a.Ti * a.Hi * a.Wi * a.Cin * sizeof(MT);
-  const unsigned long long wb = (unsigned long long)a.Cout * a.ldw * sizeof(MT);
-  // cache mode (v1.1 chunks after the first): descriptors only where a tile lies in one output frame, so that a time tap reads
-  // the cache or x for the whole tile (the kernel switches the descriptor per tap); other shapes gather through pointers
-  const unsigned long long cb = a.tmode == VT_TPAD_CACHE ? (unsigned long long)a.B * a.ncache * a.Hi * a.Wi * a.Cin * sizeof(MT) : 0ull;
-  const bool cache_ok = a.tmode != VT_TPAD_CACHE ||
-                        (FAST && (nbatch == 1 || a.ksplit) && a.prof == nullptr && cb < 0xFFFF0000ull && ((long long)a.Ho * a.Wo) % BM == 0 && a.ups_t == 0);
-  const bool buf = desc_gather_fits(a, (int)sizeof(MT)) && cache_ok &&
-                   a.KH <= 8 && a.KW <= 8;   // the per-row padding mask of the FAST form holds 8 bits per axis
-  VT_CHECK_ARG(!a.ksplit || buf, "vt_conv: split-K needs the descriptor gather");
-  // zero-padded time taps skipped per tile: the tap-walk form on descriptors, a tile inside one output frame
-  a.tskip = (FAST && buf && vt_opt(OPT_CONV_TSKIP) != 0 && a.tmode == VT_TPAD_ZERO && a.KT > 1 && a.pt > 0 && a.ups_t == 0 && !a.ksplit &&
-             nbatch == 1 && a.prof == nullptr && ((long long)a.Ho * a.Wo) % BM == 0) ? 1 : 0;
-  // K-step schedule of the 8-wave tile on descriptors (see the kernel): 16-bit operands 2 (two-group ping-pong), fp32 operands 1
-  // (software-pipelined single body), split-bf16 on its 64-byte-row ring 5; everything else -- the 4-wave tiles, the pointer form,
-  // the general (non tap-walk) form -- runs the plain loop.  (Earlier rounds kept every schedule selectable: their measurements are in
-  // DESIGN section 6, the instantiations are gone.)
-  constexpr bool EIGHT = WAVES_M * WAVES_N == 8;
-  constexpr int SCHED_BUF = !(EIGHT && FAST) ? 0
-                            : (is_split3<MT>::value ? ((ROWB == 64 && STAGES == 4) ? 5 : 0)
-                               : ((ROWB == kRowBytes && STAGES == 2) ? (is_h16<MT>::value ? 2 : 1) : 0));
+// The launch of `l` (igemm_launch_form, conv_select.h) in this instantiation of tile T, whose template arguments come from kTileShapes, the
+// table vt_conv_plan reports from.  Only what needs the template happens here: the kernel pointer by gather form (or the stamped
+// measurement kernel), its LDS attribute, the launch.
+template <typename MT, typename TOut, TileKind T, bool FAST, int LN256 = 0, int STAGES = 2, int ROWB = kRowBytes, int ACT = 0>
+int launch_variant(const IgemmLaunch& l, hipStream_t stream) {
+  constexpr TileShape S = kTileShapes[T];
+  constexpr int kDtype = is_split3<MT>::value ? VT_BF16X3 : std::is_same<MT, float>::value ? VT_F32 : std::is_same<MT, f16_t>::value ? VT_F16 : VT_BF16;
+  constexpr int SCHED_BUF = igemm_sched(T, FAST, kDtype, ROWB, STAGES);
   const void* kern = nullptr;
-  if (buf) {
-    a.x_bytes = (unsigned)xb;
-    a.w_bytes = (unsigned)wb;
-    a.c_bytes = (unsigned)cb;
-    kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, true, LN256, false, SCHED_BUF, ACT>);
-  } else if constexpr (LN256 == 2) {
-    // the paired launch exists on descriptors only (tup3_eligible asks for them: desc_gather_fits, conv_select.h); no pointer-form instantiation
-    VT_CHECK_ARG(false, "vt_time_upsample3: the descriptor gather is required (option conv_buf, tensors below 4 GiB)");
-  } else {
-    kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, false, LN256, false, 0, ACT>);
-  }
-  int lds_bytes = LDS;
   // the attribute is per device: one flag per (instantiation, gather form | measurement kernel, device)
   static std::atomic<bool> attr_done[3][kMaxDevices];
-  int ki = buf ? 1 : 0;
-  if (a.prof != nullptr) {   // vt_conv_profile: the scheduled 8-wave instantiations of bf16 and split-bf16 (no LayerNorm) carry the stamps
-    if constexpr (EIGHT && FAST && LN256 == 0 && ACT == 0 && (SCHED_BUF == 2 || SCHED_BUF == 5) && !std::is_same<MT, f16_t>::value &&
+  int ki = l.buf ? 1 : 0;
+  if (l.a.prof != nullptr) {   // vt_conv_profile: the scheduled 8-wave instantiations of bf16 and split-bf16 (no LayerNorm) carry the stamps
+    if constexpr (S.waves() == 8 && FAST && LN256 == 0 && ACT == 0 && (SCHED_BUF == 2 || SCHED_BUF == 5) && !std::is_same<MT, f16_t>::value &&
                   std::is_same<typename storage_of<MT>::type, TOut>::value) {
-      VT_CHECK_ARG(buf, "vt_conv_profile: descriptor gather only");
-      kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, WAVES_M, WAVES_N, TM, TN, FAST, ROWB, STAGES, true, 0, true, SCHED_BUF>);
-      lds_bytes = LDS + 4096;
+      VT_CHECK_ARG(l.buf, "vt_conv_profile: descriptor gather only");
+      kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, S.wm, S.wn, S.tm, S.tn, FAST, ROWB, STAGES, true, 0, true, SCHED_BUF>);
       ki = 2;
     } else {
       VT_CHECK_ARG(false, "vt_conv_profile: only the bf16 / split-bf16 8-wave 256 x 256 tile without fused LayerNorm is instrumented");
     }
+  } else if (l.buf) {
+    kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, S.wm, S.wn, S.tm, S.tn, FAST, ROWB, STAGES, true, LN256, false, SCHED_BUF, ACT>);
+  } else if constexpr (LN256 != 2) {   // the paired launch has no pointer-form instantiation (igemm_launch_form refuses it)
+    kern = reinterpret_cast<const void*>(&conv_igemm_glds_kernel<MT, TOut, S.wm, S.wn, S.tm, S.tn, FAST, ROWB, STAGES, false, LN256, false, 0, ACT>);
   }
-  if (const int rc = vt_dynamic_lds(kern, lds_bytes, attr_done[ki])) return rc;
-  const long long nblk = (long long)a.m_tiles * a.n_tiles;
+  VT_CHECK_ARG(kern != nullptr, "vt_time_upsample3: the descriptor gather is required (option conv_buf, tensors below 4 GiB)");
+  if (const int rc = vt_dynamic_lds(kern, l.lds_bytes, attr_done[ki])) return rc;
+  const long long nblk = (long long)l.a.m_tiles * l.a.n_tiles;
   VT_CHECK_ARG(nblk < (1ll << 31), "vt_conv: too many tiles (%lld)", nblk);
-  void* kargs[] = {&a};
-  VT_CHECK_HIP(hipLaunchKernel(kern, dim3((unsigned)nblk, 1, (unsigned)nbatch), dim3(THREADS), kargs, lds_bytes, stream));
+  void* kargs[] = {const_cast<ConvArgs*>(&l.a)};
+  VT_CHECK_HIP(hipLaunchKernel(kern, dim3((unsigned)nblk, 1, (unsigned)l.grid_z), dim3(64 * S.waves()), kargs, l.lds_bytes, stream));
   return VT_OK;
-}
-
-// launch_variant of tile T: the tile's template arguments come from kTileShapes, the table vt_conv_plan reports from
-template <typename MT, typename TOut, TileKind T, bool FAST, int LN256 = 0, int STAGES = 2, int ROWB = kRowBytes, int ACT = 0>
-int launch_tile(const ConvArgs& a, int nbatch, hipStream_t stream) {
-  constexpr TileShape S = kTileShapes[T];
-  return launch_variant<MT, TOut, S.wm, S.wn, S.tm, S.tn, FAST, LN256, STAGES, ROWB, ACT>(a, nbatch, stream);
 }
 
 #define VT_CHECK_VARIANT(cond) \
@@ -1554,43 +1500,45 @@ int launch_tile(const ConvArgs& a, int nbatch, hipStream_t stream) {
 
 // the pair every tile has: two-slot ring, the tap-walk form or the general gather
 template <typename MT, typename TOut, TileKind T>
-int launch_fast_or_general(const ConvArgs& a, const IgemmVariant& v, int nbatch, hipStream_t stream) {
+int launch_fast_or_general(const IgemmLaunch& l, hipStream_t stream) {
+  const IgemmVariant& v = l.v;
   VT_CHECK_VARIANT(v.ln256 == 0 && v.stages == 2 && v.rowb == kRowBytes);
-  return v.fast ? launch_tile<MT, TOut, T, true>(a, nbatch, stream) : launch_tile<MT, TOut, T, false>(a, nbatch, stream);
+  return v.fast ? launch_variant<MT, TOut, T, true>(l, stream) : launch_variant<MT, TOut, T, false>(l, stream);
 }
 
-// The instantiation the plan names (conv_decide, conv_select.h): nothing is decided here.  What a translation unit does not hold --
+// The instantiation the launch names (conv_decide, conv_select.h): nothing is decided here.  What a translation unit does not hold --
 // LayerNorm / LDS epilogue with results in another type, the 64-byte ring outside split-bf16 -- is an argument error.
 template <typename MT, typename TOut>
-int dispatch_tile(const ConvArgs& a, const IgemmVariant& v, int nbatch, hipStream_t stream) {
+int dispatch_tile(const IgemmLaunch& l, hipStream_t stream) {
+  const IgemmVariant& v = l.v;
   switch (v.tile) {
-    case TILE_256x32: return launch_fast_or_general<MT, TOut, TILE_256x32>(a, v, nbatch, stream);
-    case TILE_256x64: return launch_fast_or_general<MT, TOut, TILE_256x64>(a, v, nbatch, stream);
+    case TILE_256x32: return launch_fast_or_general<MT, TOut, TILE_256x32>(l, stream);
+    case TILE_256x64: return launch_fast_or_general<MT, TOut, TILE_256x64>(l, stream);
     case TILE_256x256:                                                                           // 8 waves
       if constexpr (is_split3<MT>::value) {
         if (v.rowb == 64) {    // 64-byte rows on a 4-slot ring, schedule 5
           VT_CHECK_VARIANT(v.fast && v.stages == 4);
-          return v.ln256 ? launch_tile<MT, TOut, TILE_256x256, true, 1, 4, 64>(a, nbatch, stream) : launch_tile<MT, TOut, TILE_256x256, true, 0, 4, 64>(a, nbatch, stream);
+          return v.ln256 ? launch_variant<MT, TOut, TILE_256x256, true, 1, 4, 64>(l, stream) : launch_variant<MT, TOut, TILE_256x256, true, 0, 4, 64>(l, stream);
         }
       } else if constexpr (std::is_same<MT, TOut>::value) {
         if constexpr (is_h16<MT>::value) {
           if (v.ln256 == 2) {  // conv_epilogue_lds256_pair: both frames of a time up-sampler pair from one accumulator row (vt_time_upsample3)
-            VT_CHECK_VARIANT(v.fast && v.stages == 2 && v.rowb == kRowBytes && a.pair_v != nullptr);
-            return launch_tile<MT, TOut, TILE_256x256, true, 2>(a, nbatch, stream);
+            VT_CHECK_VARIANT(v.fast && v.stages == 2 && v.rowb == kRowBytes && l.a.pair_v != nullptr);
+            return launch_variant<MT, TOut, TILE_256x256, true, 2>(l, stream);
           }
         }
         if (v.ln256) {         // conv_epilogue_lds256: fused LayerNorm, or ln_mode = 0 for coalesced rows
           VT_CHECK_VARIANT(v.fast && v.stages == 2 && v.rowb == kRowBytes);
-          return launch_tile<MT, TOut, TILE_256x256, true, 1>(a, nbatch, stream);
+          return launch_variant<MT, TOut, TILE_256x256, true, 1>(l, stream);
         }
       }
-      return launch_fast_or_general<MT, TOut, TILE_256x256>(a, v, nbatch, stream);
+      return launch_fast_or_general<MT, TOut, TILE_256x256>(l, stream);
     default:
       if (v.stages == 4) {     // the deep ring
         VT_CHECK_VARIANT(v.tile == TILE_128x128 && v.fast && v.ln256 == 0 && v.rowb == kRowBytes);
-        return launch_tile<MT, TOut, TILE_128x128, true, 0, 4>(a, nbatch, stream);
+        return launch_variant<MT, TOut, TILE_128x128, true, 0, 4>(l, stream);
       }
-      return launch_fast_or_general<MT, TOut, TILE_128x128>(a, v, nbatch, stream);
+      return launch_fast_or_general<MT, TOut, TILE_128x128>(l, stream);
   }
 }
 

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void conv_in8_kernel(const ConvArgs p) {
 extern "C" __attribute__((visibility("hidden"))) int vt_conv_in8_launch(const void* args, int dtype, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   ConvArgs a = *reinterpret_cast<const ConvArgs*>(args);
-  a.x_bytes = (unsigned)((unsigned long long)a.B * a.Ti * a.Hi * a.Wi * 8 * 2);
+  a.x_bytes = (unsigned)gather_extents(a, 2).x;
   a.in8_ct = a.Wo >= 128 ? 128 : a.Wo;
   a.in8_rt = 128 / a.in8_ct;
   a.in8_segs = (a.in8_ct + 2 + 63) / 64;

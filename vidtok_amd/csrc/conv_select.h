@@ -1,8 +1,10 @@
-// Which kernel / tile / epilogue / ring a vt_conv call gets.  conv_decide makes the decision ONCE per call, as a ConvPlan: vt_conv runs the
-// plan, vt_conv_plan reports it, vt_conv_work_bytes / vt_conv_profile / vt_conv_act read it (conv_igemm.hip), and the per-type translation
-// units that hold the kernel instantiations (conv_igemm_{f32,bf16,f16,x3,act}.hip) switch on its IgemmVariant.  The *_eligible predicates
-// are pure functions of the descriptor (ConvArgs) and of the option table; conv_decide is their only caller -- but for tup3_eligible, the
-// rule of the paired time up-sampler launch, which vt_time_upsample3 / vt_time_upsample3_supported apply to conv_decide's result.
+// Which kernel / tile / epilogue / ring a vt_conv call gets, and the form of its implicit-GEMM launches.  conv_decide makes the decision ONCE
+// per call, as a ConvPlan: vt_conv runs the plan, vt_conv_plan and vt_conv_launch_form report it, vt_conv_work_bytes / vt_conv_profile /
+// vt_conv_act read it (conv_igemm.hip), and the per-type translation units that hold the kernel instantiations
+// (conv_igemm_{f32,bf16,f16,x3,act}.hip) switch on an IgemmLaunch's variant and launch it as it stands.  The *_eligible predicates are pure
+// functions of the descriptor (ConvArgs) and of the option table; conv_decide is their only caller -- but for tup3_eligible, the rule of the
+// paired time up-sampler launch, which vt_time_upsample3 / vt_time_upsample3_supported apply to conv_decide's result.  igemm_launch_form is
+// the one place that fills in the rest of a launch: gather form, tile walk, skipped taps, K steps, schedule, LDS.
 #pragma once
 #include "conv_common.h"
 
@@ -16,6 +18,19 @@ namespace {
 inline bool conv_buf() { return vt_opt(OPT_CONV_BUF) != 0; }
 inline bool conv_tinner() { return vt_opt(OPT_CONV_TINNER) != 0; }
 
+// Bytes of the tensors a launch gathers from, as a buffer descriptor would have to hold them: x [B][Ti][Hi][Wi][Cin], the weight rows
+// [Cout][ldw], the cache [B][ncache][Hi][Wi][Cin] (cache mode; else 0).  A descriptor takes an extent below 4 GiB minus the out-of-range
+// marker (the kernels' kOob offset, which the hardware answers with zeros).
+struct GatherExtents {
+  unsigned long long x, w, c;
+};
+inline GatherExtents gather_extents(const ConvArgs& a, int elem_bytes) {
+  const unsigned long long pix = (unsigned long long)a.Hi * a.Wi * a.Cin * elem_bytes;
+  return {(unsigned long long)a.B * a.Ti * pix, (unsigned long long)a.Cout * a.ldw * elem_bytes,
+          a.tmode == VT_TPAD_CACHE ? (unsigned long long)a.B * a.ncache * pix : 0ull};
+}
+inline bool desc_holds(unsigned long long bytes) { return bytes < 0xFFFF0000ull; }
+
 // conv_in8_kernel (conv_in8.hip): the encoder's conv_in in a 16-bit type
 inline bool in8_eligible(const ConvArgs& a, int nbatch, int dtype, int out_dtype, bool ln_fused, int ln_mode_asked) {
   if (vt_opt(OPT_CONV_IN8) == 0 || !conv_buf() || nbatch != 1 || a.prof != nullptr) return false;
@@ -27,8 +42,7 @@ inline bool in8_eligible(const ConvArgs& a, int nbatch, int dtype, int out_dtype
   if (a.Wo < 8 || !((a.Wo % 128 == 0) || (128 % a.Wo == 0)) || ((long long)a.Ho * a.Wo) % 128 != 0) return false;
   if (ln_mode_asked != 0 && !ln_fused) return false;                                            // the LayerNorm belongs to the epilogue or to nobody
   if (a.ldy % 8 != 0 || (a.ln_mode != 0 && a.ldn % 8 != 0) || vt_opt(OPT_CONV_LDSEPI) == 0) return false;   // the epilogue's 16-byte rows
-  const unsigned long long xb = (unsigned long long)a.B * a.Ti * a.Hi * a.Wi * 8 * 2;
-  return xb < 0xFFFF0000ull;
+  return desc_holds(gather_extents(a, 2).x);
 }
 
 // 128 x 128 tile on a 4-slot ring (128 KB of LDS, three K steps of DMA in flight instead of one).  Two workgroups per CU
@@ -96,8 +110,8 @@ inline bool tile256_wanted(long long tiles) {
 
 // the gather through buffer descriptors (option conv_buf): both operands below 4 GiB minus the out-of-range marker
 inline bool desc_gather_fits(const ConvArgs& a, int elem_bytes) {
-  const unsigned long long xb = (unsigned long long)a.B * a.Ti * a.Hi * a.Wi * a.Cin * elem_bytes, wb = (unsigned long long)a.Cout * a.ldw * elem_bytes;
-  return conv_buf() && xb < 0xFFFF0000ull && wb < 0xFFFF0000ull;
+  const GatherExtents e = gather_extents(a, elem_bytes);
+  return conv_buf() && desc_holds(e.x) && desc_holds(e.w);
 }
 
 inline TileKind select_tile(const ConvArgs& a, int nbatch) {
@@ -133,10 +147,97 @@ struct IgemmVariant {
 
 enum ConvKernel { CONV_IGEMM = 0, CONV_NARROW = 2, CONV_WS2 = 3, CONV_IN8 = 4 };   // out8[6] of vt_conv_plan; 1 (conv_ws128, gone) stays reserved
 
+// K-step schedule of an instantiation on descriptors (see the kernel): the 8-wave tile's tap-walk form runs 16-bit operands on 2 (two-group
+// ping-pong), fp32 operands on 1 (software-pipelined single body), split-bf16 on its 64-byte-row ring on 5; everything else -- the 4-wave
+// tiles, the general (non tap-walk) form, and every pointer-form launch -- runs the plain loop 0.  (Earlier rounds kept every schedule
+// selectable: their measurements are in DESIGN section 6, the instantiations are gone.)  launch_variant instantiates by this function.
+constexpr int igemm_sched(TileKind tile, bool fast, int dtype, int rowb, int stages) {
+  if (tile != TILE_256x256 || !fast) return 0;
+  if (dtype == VT_BF16X3) return (rowb == 64 && stages == 4) ? 5 : 0;
+  if (rowb != kRowBytes || stages != 2) return 0;
+  return (dtype == VT_BF16 || dtype == VT_F16) ? 2 : 1;
+}
+
+// One implicit-GEMM launch, complete: launch_variant (conv_igemm_kernel.h) picks the kernel pointer of `v` and launches `a` as it stands.
+// `a` is a COPY of the ConvArgs conv_decide returns, taken when the form is computed: what a caller writes into its own ConvArgs afterwards
+// never reaches the launch.  Whatever the kernel has to see is set before igemm_launch_form runs (conv_decide's parameters), or written
+// into the launch's own `a` (vt_time_upsample3's V operand).
+struct IgemmLaunch {
+  ConvArgs a;      // the kernel's arguments, launch-form fields included (m_tiles, n_tiles, nsteps, lds_epi, hw_tiles, tskip, *_bytes)
+  IgemmVariant v;
+  int grid_z;      // nbatch, or the tap planes of split-K
+  bool buf;        // gather through buffer descriptors (a.x_bytes / w_bytes / c_bytes are their extents); false: 64-bit pointers
+  int sched;       // K-step schedule the launch runs
+  int lds_bytes;   // dynamic LDS: the ring (+ the stamp area of vt_conv_profile)
+};
+
+// The form of the launch of `a_in` in instantiation `v` on grid z `grid_z`: everything about it that is not the choice of kernel, tile and
+// epilogue -- a pure function of its arguments and the option table.  dtype / out_dtype: arithmetic and result type (vt_dtype).
+inline int igemm_launch_form(IgemmLaunch& l, const ConvArgs& a_in, const IgemmVariant& v, int grid_z, int dtype, int out_dtype) {
+  const TileShape& t = kTileShapes[v.tile];
+  const int BM = t.bm(), BN = t.bn(), elem = vt_is_h16(dtype) ? 2 : 4, BK = v.rowb / elem;   // split-bf16 steps over fp32 storage
+  l.a = a_in;
+  l.v = v;
+  l.grid_z = grid_z;
+  ConvArgs& a = l.a;
+  a.m_tiles = (a.M + BM - 1) / BM;
+  a.n_tiles = (a.Cout + BN - 1) / BN;
+  a.nsteps = v.fast ? a.ntaps * (a.Cin / BK) : (a.K + BK - 1) / BK;
+  if (a.ksplit) {
+    VT_CHECK_ARG(v.fast, "vt_conv: split-K needs the tap-walk form");
+    a.nsteps = (a.ksplit == 1 ? a.KH * a.KW : a.KW) * (a.Cin / BK);
+  }
+  const int oct_align = vt_is_h16(out_dtype) ? 8 : 4;   // elements per 16 bytes of the result type, at least a quad
+  a.lds_epi = (vt_opt(OPT_CONV_LDSEPI) != 0 && a.out_layout == VT_NDHWC && a.ldy % oct_align == 0 &&
+               (a.res_mode == VT_RES_NONE || a.ldr % oct_align == 0) && (a.ln_mode == 0 || a.ldn % oct_align == 0)) ? 1 : 0;
+  // Temporal taps: in pixel order (b,t,h,w) the frames t-1, t-2 a tile reads were last touched one whole frame of
+  // tiles earlier -- far beyond the 4 MiB L2 of its XCD -- so every kt tap came from the fabric again (the k3
+  // temporal conv of the widest level moved 3x its input).  Walking the tiles as (b, hw tile, t) puts the
+  // producers of those lines right before their consumer on the same XCD (xcd_remap keeps the sequence
+  // contiguous): 298 -> 340 TFLOP/s on that layer, +3 % on the 27-tap up-sampler conv (same-run A/B).
+  const long long hw = (long long)a.Ho * a.Wo;
+  const bool tile_in_frame = hw % BM == 0;
+  a.hw_tiles = (conv_tinner() && a.KT > 1 && a.To > 1 && tile_in_frame) ? (int)(hw / BM) : 0;
+  // cache mode (v1.1 chunks after the first): descriptors only where a tile lies in one output frame, so that a time tap reads
+  // the cache or x for the whole tile (the kernel switches the descriptor per tap); other shapes gather through pointers
+  const GatherExtents e = gather_extents(a, elem);
+  const bool alone = grid_z == 1 || a.ksplit;          // the tile index is a pixel index of the one tensor the descriptors hold
+  const bool cache_ok = a.tmode != VT_TPAD_CACHE || (v.fast && alone && a.prof == nullptr && desc_holds(e.c) && tile_in_frame && a.ups_t == 0);
+  l.buf = desc_gather_fits(a, elem) && cache_ok && a.KH <= 8 && a.KW <= 8;   // the per-row padding mask of the tap walk holds 8 bits per axis
+  VT_CHECK_ARG(!a.ksplit || l.buf, "vt_conv: split-K needs the descriptor gather");
+  // the paired launch exists on descriptors only (tup3_eligible asks for them); no pointer-form instantiation
+  VT_CHECK_ARG(v.ln256 != 2 || l.buf, "vt_time_upsample3: the descriptor gather is required (option conv_buf, tensors below 4 GiB)");
+  a.x_bytes = l.buf ? (unsigned)e.x : 0u;
+  a.w_bytes = l.buf ? (unsigned)e.w : 0u;
+  a.c_bytes = l.buf ? (unsigned)e.c : 0u;
+  // zero-padded time taps skipped per tile: the tap-walk form on descriptors, a tile inside one output frame
+  a.tskip = (v.fast && l.buf && vt_opt(OPT_CONV_TSKIP) != 0 && a.tmode == VT_TPAD_ZERO && a.KT > 1 && a.pt > 0 && a.ups_t == 0 && !a.ksplit &&
+             grid_z == 1 && a.prof == nullptr && tile_in_frame) ? 1 : 0;
+  l.sched = l.buf ? igemm_sched(v.tile, v.fast, dtype, v.rowb, v.stages) : 0;
+  l.lds_bytes = v.stages * (BM + BN) * v.rowb + (a.prof != nullptr ? 4096 : 0);
+  return VT_OK;
+}
+
+// the ConvArgs of split-K's partial launch: grid z = tap plane, each plane's walk into its fp32 plane of the scratch `work`; bias, residual
+// and rounding belong to the reduction (launch_splitk, conv_igemm.hip)
+inline ConvArgs splitk_partial_args(const ConvArgs& a, void* work) {
+  ConvArgs s = a;
+  s.ksplit = a.KT == 3 ? 1 : 2;
+  s.plane_bytes = (unsigned)((a.KT == 3 ? a.KH * a.KW : a.KW) * a.Cin * 2);
+  s.y = reinterpret_cast<char*>(work);
+  s.bias = nullptr;
+  s.res = nullptr; s.res_mode = VT_RES_NONE;
+  s.ln_mode = 0;
+  s.xs_z = 0; s.ws_z = 0; s.rs_z = 0;
+  s.ys_z = (long long)a.M * a.ldy;
+  return s;
+}
+
 struct ConvPlan {
   ConvKernel kernel;
-  IgemmVariant igemm;   // CONV_IGEMM: the whole launch ...
-  IgemmVariant split;   // ... and the tap-plane launch of split-K (splitk_planes > 0): its grid.z counts as nbatch in the rules
+  IgemmLaunch whole;    // CONV_IGEMM: the whole launch ...
+  IgemmLaunch part;     // ... and the tap-plane launch of split-K (splitk_planes > 0): its grid z counts as nbatch in the rules
+  int part_rc;          //     VT_ERR_ARG where that launch has no form (its error text is set): returned only by a call that would run it
   int splitk_planes;    // the geometry rule only (0 = none); whether the call HAS the scratch is splitk_runs (conv_igemm.hip)
   bool ln_fused;        // the LayerNorm the descriptor asks for comes from the conv kernel's epilogue
   int nbatch;
@@ -153,8 +254,8 @@ inline int splitk_planes(const vt_conv_desc* d, const ConvArgs& a, const ConvPla
   if (a.Cin % 64 != 0 || a.Cout % 128 != 0 || a.ldy != a.Cout || a.KT * a.KH * a.KW * a.Cin < 4608) return 0;
   if (a.res_mode == VT_RES_MIX || (a.res_mode == VT_RES_ADD && (a.ldr != a.Cout || a.Tr != a.To || a.res_tshift != 0))) return 0;
   if (a.tmode == VT_TPAD_CACHE && ((long long)a.Ho * a.Wo) % 256 != 0) return 0;     // the descriptor form of the cache gather: a tile inside one frame
-  const unsigned long long xb = (unsigned long long)a.B * a.Ti * a.Hi * a.Wi * a.Cin * 2, wb = (unsigned long long)a.Cout * a.ldw * 2;
-  if (xb >= 0xFFFF0000ull || wb >= 0xFFFF0000ull) return 0;
+  const GatherExtents e = gather_extents(a, 2);
+  if (!desc_holds(e.x) || !desc_holds(e.w)) return 0;
   if (tile != TILE_256x256 && tile != TILE_128x128) return 0;
   // The decision is a function of ONE CLIP's geometry (To, Ho, Wo, Cout, K) and never of B: a split launch sums its tap planes in
   // another order than a whole one, so a rule that looked at the launch's pixel count (round 4: "no more tiles than CUs") tied a
@@ -183,7 +284,7 @@ inline bool tup3_eligible(const vt_conv_desc* d, const ConvArgs& a, const ConvPl
   ConvArgs e = a;
   e.ln_mode = 0;
   if (!lds256_plain_eligible(e, p.nbatch, h16_io)) return false;
-  // ... on descriptors (launch_variant refuses the paired instantiation otherwise), a tile inside one frame, and the 8-wave tile by
+  // ... on descriptors (igemm_launch_form refuses the paired instantiation otherwise), a tile inside one frame, and the 8-wave tile by
   // select_tile's rule applied to one clip's pixels
   const long long hw = (long long)a.Ho * a.Wo;
   if (!desc_gather_fits(a, 2) || hw % 256 != 0) return false;
@@ -276,6 +377,7 @@ inline int conv_decide(const vt_conv_desc* d, ConvArgs& a, ConvPlan& p, unsigned
   a.xs_z = d->xs_z; a.ws_z = d->ws_z; a.ys_z = d->ys_z; a.rs_z = d->rs_z;
 
   a.prof = prof;
+  a.prof_mode = prof != nullptr ? vt_opt(OPT_WS_PROF_MODE) : 0;
   p = ConvPlan{};        // CONV_IGEMM, no split, nothing fused
   p.nbatch = nbatch;
 
@@ -333,26 +435,29 @@ inline int conv_decide(const vt_conv_desc* d, ConvArgs& a, ConvPlan& p, unsigned
   } else if (act == 0 && in8_eligible(a, nbatch, d->dtype, d->out_dtype, p.ln_fused, d->ln_mode)) {
     p.kernel = CONV_IN8;
   } else {
-    p.igemm = variant(a, nbatch, tile, (d->dtype == VT_BF16X3 ? VT_F32 : d->dtype) == d->out_dtype);
+    int rc = igemm_launch_form(p.whole, a, variant(a, nbatch, tile, (d->dtype == VT_BF16X3 ? VT_F32 : d->dtype) == d->out_dtype), nbatch,
+                               d->dtype, d->out_dtype);
+    if (rc != VT_OK) return rc;
     p.splitk_planes = act == 0 ? splitk_planes(d, a, p, tile) : 0;
-    if (p.splitk_planes > 0) {   // the partial launch: fp32 planes, no residual, no LayerNorm (launch_splitk)
-      ConvArgs s = a;
-      s.res_mode = VT_RES_NONE;
-      s.ln_mode = 0;
-      p.split = variant(s, p.splitk_planes, tile_for(s, p.splitk_planes), false);
+    if (p.splitk_planes > 0) {   // the partial launch: fp32 planes, no residual, no LayerNorm
+      // splitk_planes does not restate every condition of the descriptor gather (a tap axis above 8, a cache of 4 GiB): a partial launch
+      // without a form is refused where it would run (launch_splitk) -- a call without the scratch runs the whole launch all the same
+      const ConvArgs s = splitk_partial_args(a, d->work);
+      p.part_rc = igemm_launch_form(p.part, s, variant(s, p.splitk_planes, tile_for(s, p.splitk_planes), false), p.splitk_planes, d->dtype, VT_F32);
     }
+    return VT_OK;
   }
   return VT_OK;
 }
 }  // namespace
 
-// the per-type translation units (conv_igemm_*.hip): launch of the instantiation the plan names; `args` = ConvArgs, `variant` = IgemmVariant
+// the per-type translation units (conv_igemm_*.hip): launch of `launch` (an IgemmLaunch) in the instantiation its variant names
 // (an instantiation the unit does not hold is VT_ERR_ARG)
-extern "C" int vt_igemm_dispatch_f32(const void* args, const void* variant, int nbatch, void* stream);                  // fp32 -> fp32
-extern "C" int vt_igemm_dispatch_x3(const void* args, const void* variant, int nbatch, void* stream);                   // split-bf16 arithmetic, fp32 storage
-extern "C" int vt_igemm_dispatch_bf16(const void* args, const void* variant, int nbatch, int out_f32, void* stream);    // bf16 -> bf16 | fp32
-extern "C" int vt_igemm_dispatch_f16(const void* args, const void* variant, int nbatch, int out_f32, void* stream);     // fp16 -> fp16 | fp32
-extern "C" int vt_igemm_dispatch_relu(const void* args, const void* variant, int dtype, void* stream);                // conv_igemm_act.hip: + ReLU, in the arithmetic type
+extern "C" int vt_igemm_dispatch_f32(const void* launch, void* stream);                  // fp32 -> fp32
+extern "C" int vt_igemm_dispatch_x3(const void* launch, void* stream);                   // split-bf16 arithmetic, fp32 storage
+extern "C" int vt_igemm_dispatch_bf16(const void* launch, int out_f32, void* stream);    // bf16 -> bf16 | fp32
+extern "C" int vt_igemm_dispatch_f16(const void* launch, int out_f32, void* stream);     // fp16 -> fp16 | fp32
+extern "C" int vt_igemm_dispatch_relu(const void* launch, int dtype, void* stream);      // conv_igemm_act.hip: + ReLU, in the arithmetic type
 extern "C" int vt_ws2_launch(const void* conv_args, int dtype, void* stream);                         // conv_ws2.hip
 extern "C" int vt_conv_in8_launch(const void* conv_args, int dtype, void* stream);                    // conv_in8.hip
 extern "C" int vt_conv_narrow_launch(const void* conv_args, void* stream, int mode);                  // conv_narrow.hip (mode: 0 bf16, 1 fp16, 2 split-bf16: fp32 x, two passes)

@@ -159,6 +159,7 @@ SIGNATURES = {
     "vt_conv_desc_size": (C.c_int, []),
     "vt_conv_work_bytes": (_I64, [C.POINTER(ConvDesc)]),
     "vt_conv_plan": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(_I32)]),
+    "vt_conv_launch_form": (C.c_int, [C.POINTER(ConvDesc), _I32, C.POINTER(_I64)]),
     "vt_conv_profile": (C.c_int, [C.POINTER(ConvDesc), _P, _P]),
     "vt_time_upsample3_supported": (C.c_int, [C.POINTER(ConvDesc)]),
     "vt_time_upsample3": (C.c_int, [C.POINTER(ConvDesc), _P, _I32, _P]),

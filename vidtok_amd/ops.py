@@ -53,6 +53,22 @@ def conv_plan(d):
                 kernel={2: "narrow", 3: "ws2", 4: "in8"}.get(out[6], "igemm"), lds_epilogue=out[7] == 1, deep_ring=out[7] == 2)
 
 
+CONV_CALLS = {"conv": 0, "time_upsample3": 1, "conv_act": 2}
+FORM_FIELDS = ("x_bytes", "w_bytes", "c_bytes", "tskip", "hw_tiles", "lds_epi", "nsteps", "m_tiles", "n_tiles", "grid_z", "ksplit", "sched", "lds_bytes")
+
+
+def conv_launch_form(d, call="conv"):
+    """vt_conv_launch_form(d, call) -> dict: the form of the implicit-GEMM launch behind vt_conv ("conv": the partial launch where the scratch in
+    `d` makes the split run), vt_time_upsample3 or vt_conv_act with ReLU -- kernel, gather ("desc" | "ptr"), FORM_FIELDS and the instantiation
+    (tile index, fast, ln256, stages, rowb).  Launches of the ws2, narrow and in8 kernels report the kernel and zeros."""
+    out = (C.c_int64 * 16)()
+    L.check(L.load().vt_conv_launch_form(C.byref(d), CONV_CALLS[call], out), "vt_conv_launch_form")
+    form = dict(kernel={2: "narrow", 3: "ws2", 4: "in8"}.get(out[0], "igemm"), gather="desc" if out[1] else "ptr")
+    form.update(zip(FORM_FIELDS, out[2:15]))
+    form.update(tile=out[15] & 15, fast=bool(out[15] >> 4 & 15), ln256=out[15] >> 8 & 15, stages=out[15] >> 12 & 15, rowb=out[15] >> 16)
+    return form
+
+
 def replay_convs(record, conv_kernel_only=True):
     """Re-issue recorded vt_conv launches on the current stream (same descriptors, same tensors).  With
     conv_kernel_only a descriptor whose LayerNorm is not produced by the conv epilogue is replayed without it (that

@@ -18,8 +18,7 @@ import torch
 
 import arena as A
 import test_gpu_ops as T
-import test_gpu_time_upsample3 as U
-from util import rel_err
+from util import rel_err, tup3_operands, tup3_run
 from vidtok_amd import lib as L
 from vidtok_amd import ops
 from vidtok_amd.ops import ConvGeom
@@ -270,16 +269,16 @@ def test_time_upsample3(shape, C_, ln, ldv_pad, dtype, vt_opts):
     """the operator shapes of tests/test_gpu_time_upsample3.py, 16 x 48 frames (768 pixels: three tiles per frame, tile edges in mid-row),
     and V at ldv = C + 8"""
     vt_opts(conv_tile=256)
-    x, _w, bias, wu, wv, mf, gam, bet = U._operands(*shape, C_, dtype)
+    x, _w, bias, wu, wv, mf, gam, bet = tup3_operands(*shape, C_, dtype)
     lnp = (gam, bet, 1e-6, True) if ln else None
     with recording() as rec:
         if ldv_pad:
-            v = ops.conv(x, wv, None, U.G3, cout=C_, ldy=C_ + ldv_pad)
+            v = ops.conv(x, wv, None, ConvGeom(**T.G3), cout=C_, ldy=C_ + ldv_pad)
             y = torch.full((shape[0], 2 * shape[1]) + shape[2:] + (C_,), float("nan"), dtype=dtype, device=DEV)
             assert ops.time_upsample3(x, (wu, bias), v, mf, y, cout=C_) is not None, "vt_time_upsample3_supported refused a covered shape"
             torch.cuda.synchronize()
         else:
-            y, n, v = U._run(x, bias, wu, wv, mf, lnp, C_)
+            y, n, v = tup3_run(x, bias, wu, wv, mf, lnp, C_)
     assert torch.isfinite(y.float()).all()
     assert len(rec) == 2 and isinstance(rec[1][0], ops.TimeUp3Desc) and rec[1][0].ldv == C_ + ldv_pad
     _replay_check(rec[0], "paired time up-sampler: V")

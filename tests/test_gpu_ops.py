@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import torch_ops_ref as R
-from util import rel_err
+from util import ndhwc_act, rel_err, tup3_operands, tup3_run
 from vidtok_amd import lib as L
 from vidtok_amd import ops
 from vidtok_amd.ops import ConvGeom
@@ -46,11 +46,7 @@ def _rand(shape, dtype, seed, scale=1.0):
 
 def _act(B, T, H, W, c_real, dtype, seed):
     """NDHWC activation with channels padded to a multiple of 8 (pad lanes zero)."""
-    cp = ops.pad_channels(c_real)
-    x = torch.zeros((B, T, H, W, cp), dtype=dtype)
-    g = torch.Generator().manual_seed(seed)
-    x[..., :c_real] = torch.randn((B, T, H, W, c_real), generator=g).to(dtype)
-    return x.to(DEV)
+    return ndhwc_act(B, T, H, W, c_real, dtype, seed).to(DEV)
 
 
 def _cpu(kw):
@@ -1103,26 +1099,60 @@ def test_conv_interleaved_mix_with_layernorm(shape, silu, vt_opts):
     assert not isinstance(r, tuple)
 
 
-@pytest.mark.parametrize("dt", list(H16) + [torch.float32], ids=list(H16_IDS) + ["f32"])
-@pytest.mark.parametrize("cout,tile", [(128, 0), (256, 256)], ids=["lds128_epilogue", "lds256_epilogue"])
+# (cout, tile, dtype, id): tile 0 / 256 = the 128- / 256-wide tile of the implicit-GEMM kernel, "in8" = conv_in8_kernel, "paired" = the time
+# up-sampler's paired launch
+NT_SITES = [
+    (128, 0, torch.bfloat16, "lds128_epilogue-bf16"), (128, 0, F16, "lds128_epilogue-f16"), (128, 0, torch.float32, "lds128_epilogue-f32"),
+    (256, 256, torch.bfloat16, "lds256_epilogue-bf16"), (256, 256, F16, "lds256_epilogue-f16"), (256, 256, torch.float32, "lds256_epilogue-f32"),
+    (128, "in8", torch.bfloat16, "in8-bf16"), (256, "paired", torch.bfloat16, "paired-bf16"),
+]
+
+
+@pytest.mark.parametrize("cout,tile,dt", [s[:3] for s in NT_SITES], ids=[s[3] for s in NT_SITES])
 def test_conv_streaming_stores_same_bits(cout, tile, dt, vt_opts):
     """option conv_nt_mb: outputs at least that large leave the LDS epilogues as streaming (nt) stores -- a cache policy, not arithmetic:
-    y and the fused LayerNorm are the bits of the plain stores (threshold 1 MiB vs off, on a tensor of 2 / 4 MiB)."""
-    B, T, H, W = 1, 2, 64, 64
-    cin = cout
-    if tile:
-        vt_opts(conv_tile=tile)
-    x = _act(B, T, H, W, cin, dt, 1)
-    res = _act(B, T, H, W, cout, dt, 4)
-    g = torch.Generator().manual_seed(2)
-    geom = ConvGeom(kh=3, kw=3, ph=1, pw=1, ph_hi=1, pw_hi=1)
-    w = pack_conv_weight(torch.randn((cout, cin, 3, 3), generator=g) / math.sqrt(cin * 9), dt, cin_stored=cin).to(DEV)
-    bias = _rand((cout,), torch.float32, 3, 0.1)
-    ln = (_rand((cout,), torch.float32, 6, 0.5) + 1.0, _rand((cout,), torch.float32, 7, 0.2), 1e-6, True)
+    y and the fused LayerNorm are the bits of the plain stores (threshold 1 MiB vs off, on tensors of at least 1 MiB: 1 MiB exactly for in8, up to 4 MiB).  One case per
+    epilogue that stores rows from the LDS: the 128- and the 256-wide tile (residual add, LayerNorm + SiLU, y kept), conv_in8_kernel
+    (3 -> 128, 3 x 3 x 3, LayerNorm, y kept) and the paired launch of the time up-sampler (C = 256, LayerNorm)."""
+    if tile == "in8":
+        case = ("in8_nt", (1, 4, 32, 32), 3, cout, (3, 3, 3), ConvGeom(**G333), dict(ln="keep"))
+        x, w, _rows, bias, kw, (gam, bet, keep) = _conv_operands(case, dt)
+
+        def launch():
+            ops.CONV_RECORD = []
+            try:
+                out = ops.conv(x, w, bias, case[5], cout=cout, ln=(gam, bet, 1e-6, True), ln_keep_y=keep, **kw)
+                plan = ops.conv_plan(ops.CONV_RECORD[0][0])
+            finally:
+                ops.CONV_RECORD = None
+            assert plan["kernel"] == "in8", plan
+            return out
+    elif tile == "paired":
+        vt_opts(conv_tile=256)
+        x, _w, bias, wu, wv, mf, gam, bet = tup3_operands(1, 4, 32, 32, cout, dt)
+
+        def launch():
+            y, n, _v = tup3_run(x, bias, wu, wv, mf, (gam, bet, 1e-6, True), cout)
+            return y, n
+    else:
+        B, T, H, W = 1, 2, 64, 64
+        cin = cout
+        if tile:
+            vt_opts(conv_tile=tile)
+        x = _act(B, T, H, W, cin, dt, 1)
+        res = _act(B, T, H, W, cout, dt, 4)
+        g = torch.Generator().manual_seed(2)
+        geom = ConvGeom(kh=3, kw=3, ph=1, pw=1, ph_hi=1, pw_hi=1)
+        w = pack_conv_weight(torch.randn((cout, cin, 3, 3), generator=g) / math.sqrt(cin * 9), dt, cin_stored=cin).to(DEV)
+        bias = _rand((cout,), torch.float32, 3, 0.1)
+        ln = (_rand((cout,), torch.float32, 6, 0.5) + 1.0, _rand((cout,), torch.float32, 7, 0.2), 1e-6, True)
+
+        def launch():
+            return ops.conv(x, w, bias, geom, cout=cout, res=res, res_mode=L.VT_RES_ADD, ln=ln, ln_keep_y=True)
     outs = []
     for mb in (0, 1):
         vt_opts(conv_nt_mb=mb, conv_ws=0)
-        y, n = ops.conv(x, w, bias, geom, cout=cout, res=res, res_mode=L.VT_RES_ADD, ln=ln, ln_keep_y=True)
+        y, n = launch()
         torch.cuda.synchronize()
         outs.append((y.clone(), n.clone()))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])

@@ -14,15 +14,13 @@ import torch.nn.functional as F
 
 import torch_ops_ref as R  # noqa: F401  (the host statements the operator gates belong to)
 from test_gpu_ops import TOL, _act
-from util import build_model, rel_err
+from util import build_model, rel_err, tup3_operands, tup3_run
 from vidtok_amd import modules, ops
-from vidtok_amd.packing import pack_conv_weight, time_upsample3_weights
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 H16 = [torch.bfloat16, torch.float16]
 H16_IDS = ["bf16", "f16"]
-G3 = ops.ConvGeom(kh=3, kw=3, ph=1, pw=1, ph_hi=1, pw_hi=1)
 
 
 def _statement(x, w, bias, mf, ln, dtype):
@@ -40,31 +38,6 @@ def _statement(x, w, bias, mf, ln, dtype):
     return y, (n * torch.sigmoid(n) if silu else n)
 
 
-def _operands(B, T, H, W, C, dtype, seed=1):
-    gen = torch.Generator().manual_seed(seed + 1)
-    x = _act(B, T, H, W, C, dtype, seed)
-    w = torch.randn((C, C, 3, 3, 3), generator=gen) / math.sqrt(27 * C)
-    bias = (torch.randn((C,), generator=gen) * 0.1).to(DEV)
-    wu = pack_conv_weight(time_upsample3_weights(w, "u"), dtype, cin_stored=C).to(DEV)
-    wv = pack_conv_weight(time_upsample3_weights(w, "v"), dtype, cin_stored=C).to(DEV)
-    gam = (torch.randn((C,), generator=gen) * 0.5 + 1.0).to(DEV)
-    bet = (torch.randn((C,), generator=gen) * 0.2).to(DEV)
-    return x, w, bias, wu, wv, torch.tensor([0.2], device=DEV), gam, bet
-
-
-def _run(x, bias, wu, wv, mf, ln, C):
-    """V by a plain convolution, then the paired launch into NaN-filled outputs -> (y, n or None, V)"""
-    B, T, H, W, _ = x.shape
-    v = ops.conv(x, wv, None, G3, cout=C)
-    y = torch.full((B, 2 * T, H, W, C), float("nan"), dtype=x.dtype, device=DEV)
-    n = torch.full_like(y, float("nan")) if ln is not None else None
-    r = ops.time_upsample3(x, (wu, bias), v, mf, y, cout=C, ln=ln, ln_out=n)
-    torch.cuda.synchronize()
-    assert r is not None, "vt_time_upsample3_supported refused a covered shape"
-    assert isinstance(r, tuple) == (ln is not None)
-    return y, n, v
-
-
 @pytest.mark.parametrize("silu", [False, True], ids=["ln", "ln_silu"])
 @pytest.mark.parametrize("dtype", H16, ids=H16_IDS)
 def test_paired_launch_with_layernorm(dtype, silu, vt_opts):
@@ -72,9 +45,9 @@ def test_paired_launch_with_layernorm(dtype, silu, vt_opts):
     their zero time tap, both frames of a pair come interleaved out of one accumulator row, each with its own LayerNorm"""
     vt_opts(conv_tile=256)
     C = 256
-    x, w, bias, wu, wv, mf, gam, bet = _operands(2, 3, 16, 16, C, dtype)
+    x, w, bias, wu, wv, mf, gam, bet = tup3_operands(2, 3, 16, 16, C, dtype)
     ln = (gam, bet, 1e-6, silu)
-    y, n, v = _run(x, bias, wu, wv, mf, ln, C)
+    y, n, v = tup3_run(x, bias, wu, wv, mf, ln, C)
     yr, nr = _statement(x, w, bias, mf, ln, dtype)
     assert torch.isfinite(y.float()).all() and torch.isfinite(n.float()).all()
     ey, en = rel_err(y, yr), rel_err(n, nr)
@@ -89,13 +62,43 @@ def test_paired_launch_with_layernorm(dtype, silu, vt_opts):
     assert rel_err(y[1, 0], leaked) > 0.05, rel_err(y[1, 0], leaked)
 
 
+@pytest.mark.parametrize("silu", [True, False], ids=["ln_silu", "ln"])
+@pytest.mark.parametrize("dtype", H16, ids=H16_IDS)
+def test_paired_launch_with_zero_v_is_the_plain_launch(dtype, silu, vt_opts):
+    """V = 0: both frames of a pair are alpha x[j] + (1 - alpha) (U[j] + bias + 0), which is what a plain ops.conv of the same [W0 | W2]
+    rows with the alpha-mix against x and the same LayerNorm writes -- t + 0 is exact and the paired epilogue finishes a row with the
+    row phase of the 256-wide tile's plain one, so y and n are the plain launch's bit for bit (B = 2, T = 3, one tile = one frame)"""
+    from vidtok_amd import lib as L
+
+    vt_opts(conv_tile=256)
+    C = 256
+    x, _w, bias, wu, _wv, mf, gam, bet = tup3_operands(2, 3, 16, 16, C, dtype)
+    ln = (gam, bet, 1e-6, silu)
+    y = torch.full((2, 6, 16, 16, C), float("nan"), dtype=dtype, device=DEV)
+    n = torch.full_like(y, float("nan"))
+    r = ops.time_upsample3(x, (wu, bias), torch.zeros_like(x), mf, y, cout=C, ln=ln, ln_out=n)
+    assert isinstance(r, tuple), "the paired launch serves this shape and takes the LayerNorm"
+    ops.CONV_RECORD = []
+    try:
+        y_plain, n_plain = ops.conv(x, wu, bias, ops.TUP3_GEOM, cout=C, res=x, res_mode=L.VT_RES_MIX, mix_factor=mf, ln=ln)
+        plan = ops.conv_plan(ops.CONV_RECORD[0][0])
+    finally:
+        ops.CONV_RECORD = None
+    torch.cuda.synchronize()
+    assert plan["kernel"] == "igemm" and plan["tile"] == (256, 256) and plan["ln_fused"], plan
+    assert torch.isfinite(n_plain.float()).all()
+    for q in (0, 1):
+        assert torch.equal(y[:, q::2], y_plain), f"y, frames 2j + {q}"
+        assert torch.equal(n[:, q::2], n_plain), f"n, frames 2j + {q}"
+
+
 @pytest.mark.parametrize("dtype", H16, ids=H16_IDS)
 def test_paired_launch_two_channel_tiles(dtype, vt_opts):
     """512 -> 512 on 16 x 32 frames without LayerNorm: two channel tiles (the channel offset into V and x) and two pixel tiles per frame"""
     vt_opts(conv_tile=256)
     C = 512
-    x, w, bias, wu, wv, mf, _g, _b = _operands(1, 2, 16, 32, C, dtype)
-    y, n, _ = _run(x, bias, wu, wv, mf, None, C)
+    x, w, bias, wu, wv, mf, _g, _b = tup3_operands(1, 2, 16, 32, C, dtype)
+    y, n, _ = tup3_run(x, bias, wu, wv, mf, None, C)
     yr, _ = _statement(x, w, bias, mf, None, dtype)
     assert torch.isfinite(y.float()).all()
     e = rel_err(y, yr)
@@ -108,8 +111,8 @@ def test_paired_launch_single_frame(dtype, vt_opts):
     """T = 1: both output frames come from j = 0 (no V[j-1] anywhere)"""
     vt_opts(conv_tile=256)
     C = 256
-    x, w, bias, wu, wv, mf, _g, _b = _operands(1, 1, 16, 16, C, dtype)
-    y, _, _ = _run(x, bias, wu, wv, mf, None, C)
+    x, w, bias, wu, wv, mf, _g, _b = tup3_operands(1, 1, 16, 16, C, dtype)
+    y, _, _ = tup3_run(x, bias, wu, wv, mf, None, C)
     yr, _ = _statement(x, w, bias, mf, None, dtype)
     assert torch.isfinite(y.float()).all()
     e = rel_err(y, yr)
@@ -147,7 +150,7 @@ def test_refused_shapes_fall_back_bit_for_bit(shape, dtype, vt_opts):
     vt_opts(conv_tile=256)
     C = 256
     m, norm = _upsampler(C)
-    x, _w, _bias, _wu, _wv, mf, _g, _b = _operands(*shape, C, dtype)
+    x, _w, _bias, _wu, _wv, mf, _g, _b = tup3_operands(*shape, C, dtype)
     y = torch.empty((shape[0], 2 * shape[1]) + shape[2:] + (C,), dtype=dtype, device=DEV)
     refused = lambda: pytest.fail("nothing is packed or computed for a refused launch")      # noqa: E731
     assert ops.time_upsample3(x, refused, refused, mf, y, cout=C) is None             # (fp32: the library itself answers no)

@@ -156,3 +156,45 @@ def cpu_autocast_usable(dtype, factor=6.0):
         _FP16_PROBE[dtype] = t16 < max(0.25, factor * t32)
         print(f"[cpu_autocast_usable] conv3d 3x3x3 64->64 on 3x32x32: fp32 {t32:.3f} s, autocast({dtype}) {t16:.3f} s -> usable {_FP16_PROBE[dtype]}")
     return _FP16_PROBE[dtype]
+
+
+def ndhwc_act(B, T, H, W, c_real, dtype, seed):
+    """NDHWC activation (on the host) with channels padded to a multiple of 8 (pad lanes zero)."""
+    from vidtok_amd import ops
+
+    cp = ops.pad_channels(c_real)
+    x = torch.zeros((B, T, H, W, cp), dtype=dtype)
+    g = torch.Generator().manual_seed(seed)
+    x[..., :c_real] = torch.randn((B, T, H, W, c_real), generator=g).to(dtype)
+    return x
+
+
+def tup3_operands(B, T, H, W, C, dtype, seed=1, device="cuda"):
+    """the operands of a causal v1.0 time up-sampler in its three-product form (vt_time_upsample3) on `device`:
+    (x, w [C, C, 3, 3, 3] on the host, bias, packed [W0 | W2] rows, packed W1 rows, mix factor, LayerNorm gamma, beta)"""
+    from vidtok_amd.packing import pack_conv_weight, time_upsample3_weights
+
+    gen = torch.Generator().manual_seed(seed + 1)
+    x = ndhwc_act(B, T, H, W, C, dtype, seed).to(device)
+    w = torch.randn((C, C, 3, 3, 3), generator=gen) / math.sqrt(27 * C)
+    bias = (torch.randn((C,), generator=gen) * 0.1).to(device)
+    wu = pack_conv_weight(time_upsample3_weights(w, "u"), dtype, cin_stored=C).to(device)
+    wv = pack_conv_weight(time_upsample3_weights(w, "v"), dtype, cin_stored=C).to(device)
+    gam = (torch.randn((C,), generator=gen) * 0.5 + 1.0).to(device)
+    bet = (torch.randn((C,), generator=gen) * 0.2).to(device)
+    return x, w, bias, wu, wv, torch.tensor([0.2], device=device), gam, bet
+
+
+def tup3_run(x, bias, wu, wv, mf, ln, C):
+    """V by a plain convolution, then the paired launch into NaN-filled outputs -> (y, n or None, V)"""
+    from vidtok_amd import ops
+
+    B, T, H, W, _ = x.shape
+    v = ops.conv(x, wv, None, ops.ConvGeom(kh=3, kw=3, ph=1, pw=1, ph_hi=1, pw_hi=1), cout=C)
+    y = torch.full((B, 2 * T, H, W, C), float("nan"), dtype=x.dtype, device=x.device)
+    n = torch.full_like(y, float("nan")) if ln is not None else None
+    r = ops.time_upsample3(x, (wu, bias), v, mf, y, cout=C, ln=ln, ln_out=n)
+    torch.cuda.synchronize()
+    assert r is not None, "vt_time_upsample3_supported refused a covered shape"
+    assert isinstance(r, tuple) == (ln is not None)
+    return y, n, v

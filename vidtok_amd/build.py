@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvidtok_amd.so")
 SOURCES = ["conv_igemm_bf16.hip", "conv_igemm_f16.hip", "conv_igemm_f32.hip", "conv_igemm_x3.hip", "conv_igemm_act.hip", "conv_igemm.hip", "conv_in8.hip", "conv_ws2.hip", "conv_narrow.hip", "tblock_ws128.hip", "attention.hip", "pointwise.hip", "groupnorm.hip", "regularizers.hip", "metrics.hip", "lpips.hip", "lpips_grad.hip", "video_io.hip", "segments.hip", "grad.hip", "grad_decoder.hip", "packing.hip", "error.cpp", "options.cpp", "model.cpp"]
-HEADERS = ["common.h", "conv_common.h", "conv_select.h", "conv_igemm_kernel.h", "options.h", "row8.h", os.path.join("..", "..", "include", "vidtok_amd.h")]
+HEADERS = ["common.h", "conv_common.h", "conv_rows.h", "conv_select.h", "conv_igemm_kernel.h", "options.h", "row8.h", os.path.join("..", "..", "include", "vidtok_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-file additions.  conv_ws2.hip: its row arithmetic runs beside the partner wave's MFMAs, where packed fp32
 # (v_pk_*_f32, what the SLP vectoriser makes of eight parallel scalar chains) stalls the matrix pipe
@@ -27,12 +27,15 @@ EXTRA_FLAGS = {"conv_ws2.hip": ["-fno-slp-vectorize"], "tblock_ws128.hip": ["-fn
 
 # objects whose kernels keep operands in hand-assigned registers around inline-asm MFMAs (weights in the accumulator half, results read behind
 # explicit wait states): a register spill there is not a slow-down but a wrong result (round 6: the fp16 fused temporal block with 16 spilled
-# registers computed garbage) -- the build refuses it.  Instantiations with cycle stamps (measurement aids, last template argument true) may spill.
-NO_SPILL = {"tblock_ws128.hip": "tblock_pair_kernel", "conv_ws2.hip": "conv3x3_ws2_kernel",
+# registers computed garbage) -- the build refuses it.  Instantiations with cycle stamps (measurement aids, last template argument PROF = true) may
+# spill: PROF_LAST names the kernels whose last template argument is PROF.  conv_in8_kernel<H, REPL> ends in a bool too, but REPL (replicate time
+# padding) is no measurement flag: all four instantiations are checked.
+NO_SPILL = {"tblock_ws128.hip": "tblock_pair_kernel", "conv_ws2.hip": "conv3x3_ws2_kernel", "conv_in8.hip": "conv_in8_kernel",
             # the paired epilogue of vt_time_upsample3 (LN256 = 2: the template arguments end BUF, 2, PROF = false, SCHED, ACT = 0) holds two more
             # operand rows per output row than conv_epilogue_lds256 beside the parked accumulators; spilled, it would be slow, not wrong -- refused all the same
             "conv_igemm_bf16.hip": re.compile(r"conv_igemm_glds_kernel.*Lb[01]ELi2ELb0ELi\dELi0EEEvNS_8ConvArgsE$"),
             "conv_igemm_f16.hip": re.compile(r"conv_igemm_glds_kernel.*Lb[01]ELi2ELb0ELi\dELi0EEEvNS_8ConvArgsE$")}
+PROF_LAST = ("tblock_pair_kernel", "conv3x3_ws2_kernel")
 LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 
 
@@ -61,7 +64,7 @@ def check_no_spill(objdir):
     for src, kern in NO_SPILL.items():
         obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
         for name, _v, _a, spill, scratch in kernel_resources(obj):
-            measured = name.endswith("Lb1EEEvNS_10TBlockArgsE") or name.endswith("Lb1EEEvNS_8ConvArgsE")      # PROF = true
+            measured = any(k in name for k in PROF_LAST) and name.endswith(("Lb1EEEvNS_10TBlockArgsE", "Lb1EEEvNS_8ConvArgsE"))      # PROF = true
             hit = kern in name if isinstance(kern, str) else kern.search(name) is not None
             if hit and not measured and (spill or scratch):
                 bad.append(f"{name}: {spill} spilled registers, {scratch} B scratch")

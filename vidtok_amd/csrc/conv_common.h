@@ -205,9 +205,10 @@ struct Oct;
 // A 16-byte streaming store.  Inline assembly on purpose: written as `if (nt) __builtin_nontemporal_store(..) else plain store` the two
 // stores to one address are merged by the optimiser into ONE plain store -- the hint vanishes (round 6: the first build of option
 // conv_nt_mb compiled to 688 global_store_dwordx4 and not one "nt"; measured, it did nothing).  The compiler's wait-count bookkeeping
-// does not see the store; nothing ever waits on it, and unseen stores can only make a counted wait for a later load stricter.
+// does not see the store; nothing ever waits on it, and unseen stores can only make a counted wait for a later load stricter.  Nor does it
+// pad the store's hazard: the s_nop 1 inside the string keeps the next instruction from overwriting the data registers before the store has read them.
 __device__ __forceinline__ void store16_nt(void* p, const u32x4& v) {
-  asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(p), "v"(v) : "memory");
+  asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
 template <>

@@ -40,12 +40,9 @@
 
 #pragma once
 #include "conv_select.h"
+#include "conv_rows.h"
 
 namespace {
-
-// ReLU of the ACT = VT_ACT_RELU epilogues (vt_conv_act): a select, so that -0 and negative results both become +0 (max-pooling the
-// features afterwards is then bit-equal to torch's max_pool2d of them)
-__device__ __forceinline__ float act_relu(float v) { return v > 0.0f ? v : 0.0f; }
 
 // Epilogue shared by both staging variants: + bias, + residual / alpha-mix, dtype conversion, NDHWC
 // vector store (lane = one pixel, 4 consecutive channels per accumulator quad) or NCTHW fp32 store.
@@ -187,20 +184,20 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[T
 // byte-bound.  Here the tile (+ bias) is transposed through the LDS the K loop no longer needs (128 x 128 fp32 =
 // the 64 KiB of the two stages): every lane then handles 8 consecutive channels of a pixel row with 16 lanes per
 // 128 channels, so a wave instruction covers whole 128-B lines (4 rows x 256 B bf16, 4 rows x 512 B fp32).
-//   LDS layout: T[pixel][32 chunks of 4 floats], chunk index XOR (pixel & 31): the 8 lanes a ds_write_b128 services
-//   together hold 8 different pixels of one chunk -> 8 different columns; a ds_read_b128 group reads 16 different
+//   LDS layout: T[pixel][32 chunks of 4 floats], swizzled (rows_chunk, conv_rows.h); a ds_read_b128 group reads 16 different
 //   chunks of one row -> 16 different bank quads.
 // (ALLOW_RES = false: an instantiation for launches that never carry a residual, without the eight residual rows' registers.
 // NA x NB: the wave's accumulators cover channels [c_base, c_base + 32 NA) x pixel rows [prow_base, prow_base + 32 NB) of the tile:
-// 2 x 2 at (64 wn, 64 wm) for the implicit-GEMM kernel's wave grid.  conv_in8_kernel's 1 x 4 grid has its own two-pass copy of this
-// row phase, conv_epilogue_in8, on a 64-row buffer.)
+// 2 x 2 at (64 wn, 64 wm) for the implicit-GEMM kernel's wave grid.  The layout and the row phase are conv_rows.h's, W = 128, scalar rows;
+// conv_in8_kernel's 1 x 4 grid runs the same pieces on a 64-row buffer, conv_epilogue_in8.)
 template <typename TOut, bool ALLOW_RES = true, int NA = 2, int NB = 2, int ACT = 0>
 __device__ __forceinline__ void conv_epilogue_lds128_at(const ConvArgs& p, f32x16 (&acc)[NA][NB], int m_blk, int n_blk, int c_base,
                                                         int prow_base, int lane, int tid, char* smem, long long z) {
   TOut* __restrict__ yg = reinterpret_cast<TOut*>(p.y) + z * p.ys_z;
   const TOut* __restrict__ rg = reinterpret_cast<const TOut*>(p.res) + z * p.rs_z;
+  TOut* __restrict__ ng = reinterpret_cast<TOut*>(p.ln_out);
   float* T = reinterpret_cast<float*>(smem);
-  const bool has_res = ALLOW_RES && p.res_mode != VT_RES_NONE;
+  const int res_mode = ALLOW_RES ? p.res_mode : VT_RES_NONE;
   float alpha = 0.0f;
   if (p.res_mode == VT_RES_MIX) alpha = 1.0f / (1.0f + __expf(-p.mix_factor[0]));
   // read-back mapping: 16 lanes per pixel row, 8 consecutive channels each (two adjacent 16-B chunks of the row:
@@ -211,7 +208,7 @@ __device__ __forceinline__ void conv_epilogue_lds128_at(const ConvArgs& p, f32x1
   const int row0 = tid >> 4;
   // residual first: its latency rides under the transposition
   Oct<TOut> rq[ALLOW_RES ? NT : 1];
-  if (has_res) {
+  if (res_mode != VT_RES_NONE) {
     const bool remap = p.res_tshift != 0 || p.Tr != p.To;   // uniform
     const long long HWo = (long long)p.Ho * p.Wo;
     long long mres[NT];
@@ -231,78 +228,27 @@ __device__ __forceinline__ void conv_epilogue_lds128_at(const ConvArgs& p, f32x1
     for (int it = 0; it < NT; ++it) rq[it].load(rg + mres[it] * p.ldr + n_blk + 8 * oct_j);
   }
   __syncthreads();                            // every wave has finished reading the last stage
-  {
-    const int h = lane >> 5;
 #pragma unroll
-    for (int a = 0; a < NA; ++a)
+  for (int a = 0; a < NA; ++a)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int c = c_base + 32 * a + 8 * g + 4 * h;         // first channel of the quad inside the tile
-        f32x4 bq;
-        if (p.bias) bq = *reinterpret_cast<const f32x4*>(p.bias + n_blk + c);
-        else bq[0] = bq[1] = bq[2] = bq[3] = 0.0f;
+    for (int g = 0; g < 4; ++g) {
+      const int c = c_base + 32 * a + 8 * g + 4 * (lane >> 5);   // first channel of the quad inside the tile
+      const f32x4 bq = rows_bias(p.bias, n_blk + c);
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const int prow = prow_base + b * 32 + (lane & 31);
-          f32x4 v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = acc[a][b][4 * g + e] + bq[e];
-          *reinterpret_cast<f32x4*>(T + prow * 128 + (((c >> 2) ^ (prow & 31)) << 2)) = v;
-        }
-      }
-  }
+      for (int b = 0; b < NB; ++b) rows_scatter<128>(T, prow_base + b * 32 + (lane & 31), c, acc[a][b], g, bq);
+    }
   __syncthreads();
   // fused LayerNorm (+SiLU) of the finished rows (launcher: Cout = 128, so the 16 lanes of a row hold all of it)
   float lg[8], lb[8];
-  TOut* __restrict__ ng = reinterpret_cast<TOut*>(p.ln_out);
-  if (p.ln_mode) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      lg[e] = ln_fold(p.ln_gamma[8 * oct_j + e], sizeof(TOut) == 2 && p.ln_mode == 2);     // 16-bit storage + SiLU: the affine carries -log2(e)
-      lb[e] = ln_fold(p.ln_beta[8 * oct_j + e], sizeof(TOut) == 2 && p.ln_mode == 2);
-    }
-  }
+  if (p.ln_mode) rows_affine(p, oct_j, sizeof(TOut) == 2 && p.ln_mode == 2, lg, lb);
 #pragma unroll
   for (int it = 0; it < NT; ++it) {
     const int row = row0 + 16 * it;
-    const int sw = row & 31;
-    const f32x4 t0 = *reinterpret_cast<const f32x4*>(T + row * 128 + (((2 * oct_j) ^ sw) << 2));
-    const f32x4 t1 = *reinterpret_cast<const f32x4*>(T + row * 128 + (((2 * oct_j + 1) ^ sw) << 2));
     float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      v[e] = e < 4 ? t0[e] : t1[e - 4];
-      if (ALLOW_RES && p.res_mode == VT_RES_ADD) v[e] = rq[it].get(e) + v[e];
-      if (ALLOW_RES && p.res_mode == VT_RES_MIX) v[e] = alpha * rq[it].get(e) + (1.0f - alpha) * v[e];
-      if constexpr (ACT == VT_ACT_RELU) v[e] = act_relu(v[e]);
-    }
+    rows_read<128>(T, row, oct_j, v);
     const long long orow = out_row(p, m_blk + row);
-    if (!p.ln_mode || p.ln_keep_y) Oct<TOut>::store(yg + orow * p.ldy + n_blk + 8 * oct_j, v, p.nt_store != 0);
-    if (p.ln_mode) {   // uniform; statistics of the fp32 row, taken before the rounding to TOut
-      float o[8];
-      if constexpr (sizeof(TOut) == 2) {   // 16-bit storage: the one-pass form every fused LayerNorm site of these modes shares (ln_row8, common.h; lg / lb folded above)
-        if (p.ln_mode == 2) ln_row8<16, true>(v, lg, lb, p.ln_eps, o);
-        else ln_row8<16, false>(v, lg, lb, p.ln_eps, o);
-      } else {                              // fp32 storage (fp32 / split-bf16 modes): two-pass statistics like layernorm_act_kernel
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[e];
-        const float mean = group_sum_dpp<16>(s) * (1.0f / 128.0f);
-        float q = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          v[e] -= mean;
-          q += v[e] * v[e];
-        }
-        const float rstd = __builtin_amdgcn_rsqf(group_sum_dpp<16>(q) * (1.0f / 128.0f) + p.ln_eps);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float u = v[e] * rstd * lg[e] + lb[e];
-          o[e] = (p.ln_mode == 2) ? silu_fast(u) : u;
-        }
-      }
-      Oct<TOut>::store(ng + orow * p.ldn + 8 * oct_j, o, p.nt_store != 0);
-    }
+    rows_finish<16, TOut, ACT>(p, res_mode, v, rq[ALLOW_RES ? it : 0], alpha, lg, lb, yg + orow * p.ldy + n_blk + 8 * oct_j,
+                               ng + orow * p.ldn + 8 * oct_j);
   }
 }
 
@@ -310,6 +256,18 @@ template <typename TOut, int ACT = 0>
 __device__ __forceinline__ void conv_epilogue_lds128(const ConvArgs& p, f32x16 (&acc)[2][2], int m_blk, int n_blk, int wm,
                                                      int wn, int lane, int tid, char* smem, long long z) {
   conv_epilogue_lds128_at<TOut, true, 2, 2, ACT>(p, acc, m_blk, n_blk, wn * 64, wm * 64, lane, tid, smem, z);
+}
+
+// One pixel half PZ of the 8-wave tile's accumulators (+ bias) into T: wave (wm, wn) holds channels [128 wn, + 128) of T rows [32 wm, + 32)
+template <int PZ>
+__device__ __forceinline__ void lds256_scatter_half(const ConvArgs& p, f32x16 (&acc)[4][2], float* T, int n_blk, int wm, int wn, int lane) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int c = wn * 128 + 32 * a + 8 * g + 4 * (lane >> 5);
+      rows_scatter<256>(T, wm * 32 + (lane & 31), c, acc[a][PZ], g, rows_bias(p.bias, n_blk + c));
+    }
 }
 
 // LayerNorm-fusing / row-coalescing epilogue of the 8-wave 256 x 256 tile (Cout % 256 == 0; with a LayerNorm: Cout = 256, so the two
@@ -323,39 +281,23 @@ __device__ __forceinline__ void conv_epilogue_lds128(const ConvArgs& p, f32x16 (
 // Also the epilogue of launches WITHOUT a LayerNorm (ln_mode 0; any Cout % 256 == 0: n_blk = the tile's first channel): the
 // transposition alone turns the 8-byte pieces of the MFMA layout into 16-byte accesses covering whole lines, for the stores and for
 // the residual / alpha-mix operand (the vector epilogue's wave store is 64 separate 8-B transactions).
-// LDS layout: T[128 rows][64 chunks of 4 floats], chunk index XOR (row & 63); row w*32 + l of half b = tile pixel
+// LDS layout: T[128 rows][64 chunks of 4 floats], swizzled (rows_chunk, conv_rows.h); row w*32 + l of half b = tile pixel
 // w*64 + b*32 + l.  A lane's two chunks (2j, 2j+1) make its ds_read_b128 pair 2-way bank-conflicted (16 lanes of a service
 // group hit 8 bank quads); the LDS is idle here, the global accesses are what counts.
 template <typename TOut, int ACT = 0>
 __device__ __forceinline__ void conv_epilogue_lds256(const ConvArgs& p, f32x16 (&acc)[4][2], int m_blk, int n_blk, int wm, int wn, int lane,
                                                      int tid, char* smem, long long z) {
-#pragma clang fp contract(off)
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   TOut* __restrict__ yg = reinterpret_cast<TOut*>(p.y) + z * p.ys_z;
   const TOut* __restrict__ rg = reinterpret_cast<const TOut*>(p.res) + z * p.rs_z;
   TOut* __restrict__ ng = reinterpret_cast<TOut*>(p.ln_out);
   float* T = reinterpret_cast<float*>(smem);
   const bool has_res = p.res_mode != VT_RES_NONE;
-  const bool has_ln = p.ln_mode != 0;                    // uniform
   float alpha = 0.0f;
   if (p.res_mode == VT_RES_MIX) alpha = 1.0f / (1.0f + __expf(-p.mix_factor[0]));
   constexpr int RS = 16;                                // T rows per sweep of the block (32 lanes per row)
   const int j = tid & 31, rsub = tid >> 5;              // lane j: channels [8j, 8j+8) of T rows rsub + RS it
   f32x2 lg[4], lb[4];
-  if (has_ln) {
-    const f32x4 g0 = *reinterpret_cast<const f32x4*>(p.ln_gamma + 8 * j), g1 = *reinterpret_cast<const f32x4*>(p.ln_gamma + 8 * j + 4);
-    const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.ln_beta + 8 * j), b1 = *reinterpret_cast<const f32x4*>(p.ln_beta + 8 * j + 4);
-    lg[0] = f32x2{g0[0], g0[1]}; lg[1] = f32x2{g0[2], g0[3]}; lg[2] = f32x2{g1[0], g1[1]}; lg[3] = f32x2{g1[2], g1[3]};
-    lb[0] = f32x2{b0[0], b0[1]}; lb[1] = f32x2{b0[2], b0[3]}; lb[2] = f32x2{b1[0], b1[1]}; lb[3] = f32x2{b1[2], b1[3]};
-    if (sizeof(TOut) == 2 && p.ln_mode == 2) {            // 16-bit storage + SiLU: the affine carries -log2(e) (ln_row8, common.h)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        lg[q] = lg[q] * kNegLog2e;
-        lb[q] = lb[q] * kNegLog2e;
-      }
-    }
-  }
-  const int h = lane >> 5;
+  if (p.ln_mode) rows_affine(p, j, sizeof(TOut) == 2 && p.ln_mode == 2, lg, lb);
   auto half = [&](auto pz_c) {
     constexpr int PZ = decltype(pz_c)::value;            // compile-time: acc[.][PZ] must not become a dynamic register index
     // tile pixel of T row r = rsub + RS it:  (r >> 5) * 64 + PZ * 32 + (r & 31)   (rsub < RS, RS divides 32: r >> 5 = it RS >> 5)
@@ -368,91 +310,15 @@ __device__ __forceinline__ void conv_epilogue_lds256(const ConvArgs& p, f32x16 (
       }
     }
     __syncthreads();                                    // K loop / previous half: everybody is done with this LDS
-    {
-      const int prl = wm * 32 + (lane & 31);
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int c = wn * 128 + 32 * a + 8 * g + 4 * h;
-          f32x4 bq;
-          if (p.bias) bq = *reinterpret_cast<const f32x4*>(p.bias + n_blk + c);
-          else bq[0] = bq[1] = bq[2] = bq[3] = 0.0f;
-          f32x4 v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = acc[a][PZ][4 * g + e] + bq[e];
-          *reinterpret_cast<f32x4*>(T + prl * 256 + (((c >> 2) ^ (prl & 63)) << 2)) = v;
-        }
-    }
+    lds256_scatter_half<PZ>(p, acc, T, n_blk, wm, wn, lane);
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
-      const int r = rsub + RS * it;
       const int m = m_blk + ((RS * it) >> 5) * 64 + PZ * 32 + rsub + ((RS * it) & 31);
       const long long orow = out_row(p, m);
-      const f32x4 t0 = *reinterpret_cast<const f32x4*>(T + r * 256 + (((2 * j) ^ (r & 63)) << 2));
-      const f32x4 t1 = *reinterpret_cast<const f32x4*>(T + r * 256 + (((2 * j + 1) ^ (r & 63)) << 2));
-      f32x2 v[4] = {f32x2{t0[0], t0[1]}, f32x2{t0[2], t0[3]}, f32x2{t1[0], t1[1]}, f32x2{t1[2], t1[3]}};
-      if (p.res_mode == VT_RES_ADD) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = f32x2{rq[it].get(2 * q), rq[it].get(2 * q + 1)} + v[q];
-      } else if (p.res_mode == VT_RES_MIX) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = f32x2{rq[it].get(2 * q), rq[it].get(2 * q + 1)} * alpha + v[q] * (1.0f - alpha);
-      }
-      if constexpr (ACT == VT_ACT_RELU) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = f32x2{act_relu(v[q][0]), act_relu(v[q][1])};
-      }
-      if (p.ln_keep_y || !has_ln) {
-        const float yv[8] = {v[0][0], v[0][1], v[1][0], v[1][1], v[2][0], v[2][1], v[3][0], v[3][1]};
-        Oct<TOut>::store(yg + orow * p.ldy + n_blk + 8 * j, yv, p.nt_store != 0);
-      }
-      if (!has_ln) continue;
-      float o[8];
-      if constexpr (sizeof(TOut) == 2) {
-        // 16-bit storage: the one-pass form of ln_row8 (common.h) on channel pairs -- both moments together, t = x rstd - mean rstd, and
-        // for SiLU a = t g' + b' with -log2(e) folded into lg / lb above: u sigmoid(u) = a * rcp(fma(2^a, -log2e, -log2e))
-        const f32x2 s = (v[0] + v[1]) + (v[2] + v[3]);
-        f32x2 qq = v[0] * v[0];
-#pragma unroll
-        for (int q = 1; q < 4; ++q) qq = __builtin_elementwise_fma(v[q], v[q], qq);
-        float nm;
-        const float rstd = ln_row_stats<32>(s[0] + s[1], qq[0] + qq[1], p.ln_eps, &nm);
-        const f32x2 rstd2 = {rstd, rstd}, nm2 = {nm, nm}, c2 = {kNegLog2e, kNegLog2e};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          f32x2 u = __builtin_elementwise_fma(__builtin_elementwise_fma(v[q], rstd2, nm2), lg[q], lb[q]);
-          if (p.ln_mode == 2) {
-            const f32x2 den = __builtin_elementwise_fma(f32x2{__builtin_amdgcn_exp2f(u[0]), __builtin_amdgcn_exp2f(u[1])}, c2, c2);
-            u = u * f32x2{__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-          }
-          o[2 * q] = u[0];
-          o[2 * q + 1] = u[1];
-        }
-      } else {
-        const f32x2 s = (v[0] + v[1]) + (v[2] + v[3]);
-        const float mean = group_sum_dpp<32>(s[0] + s[1]) * (1.0f / 256.0f);
-        f32x2 d[4], qq = {0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          d[q] = v[q] - mean;
-          qq = __builtin_elementwise_fma(d[q], d[q], qq);
-        }
-        const float rstd = __builtin_amdgcn_rsqf(__builtin_fmaf(group_sum_dpp<32>(qq[0] + qq[1]), 1.0f / 256.0f, p.ln_eps));
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          f32x2 u = __builtin_elementwise_fma(d[q] * rstd, lg[q], lb[q]);
-          if (p.ln_mode == 2) {                            // u * sigmoid(u), the arithmetic of silu_fast on a pair
-            const f32x2 t = u * -1.4426950408889634f;
-            const f32x2 e = f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + 1.0f;
-            u = u * f32x2{__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
-          }
-          o[2 * q] = u[0];
-          o[2 * q + 1] = u[1];
-        }
-      }
-      Oct<TOut>::store(ng + orow * p.ldn + 8 * j, o, p.nt_store != 0);
+      f32x2 v[4];
+      rows_read<256>(T, rsub + RS * it, j, v);
+      rows_finish<32, TOut, ACT>(p, p.res_mode, v, rq[it], alpha, lg, lb, yg + orow * p.ldy + n_blk + 8 * j, ng + orow * p.ldn + 8 * j);
     }
   };
   half(std::integral_constant<int, 0>{});
@@ -463,23 +329,20 @@ __device__ __forceinline__ void conv_epilogue_lds256(const ConvArgs& p, f32x16 (
 // convolves [W0 | W2] over (x[j-1], x[j]): the accumulator row of frame j is U[j], shared by both output frames of the pair, and with
 // V = W1 x (a plain launch of its own, p.pair_v, rows indexed like x)
 //   y[2j + q] = alpha x[j] + (1 - alpha) (U[j] + bias + V[j - 1 + q]),   q = 0, 1,   V[-1] = 0 at the start of every clip
-// -- three frame products for two frames where the two parity launches ran four.  The transposition, the lane -> (row, 8 channels)
-// map, the row arithmetic and the LayerNorm are those of conv_epilogue_lds256; every T row is read once and leaves as two y rows (and
-// two LayerNorm rows, each from its own unrounded row).  A tile lies in one frame (the serving rule, conv_select.h), so "first frame of
-// a clip" is uniform.  The V rows of a half are requested inside the row loop in two batches of four rows (beside the eight mix rows
-// requested up front: all sixteen at once would not fit the registers while the second half's accumulators are live).
+// -- three frame products for two frames where the two parity launches ran four.  Its own: the frame arithmetic, the V loads, t + V, and
+// that every T row is read once and leaves as two y rows (and two LayerNorm rows, each from its own unrounded row); the rest is the row
+// phase of conv_rows.h on pair rows, the alpha-mix against x[j].  A tile lies in one frame (the serving rule, conv_select.h), so "first
+// frame of a clip" is uniform.  The V rows of a half are requested inside the row loop in two batches of four rows (beside the eight mix
+// rows requested up front: all sixteen at once would not fit the registers while the second half's accumulators are live).
 template <typename TOut>
 __device__ __forceinline__ void conv_epilogue_lds256_pair(const ConvArgs& p, f32x16 (&acc)[4][2], int m_blk, int n_blk, int wm, int wn, int lane,
                                                           int tid, char* smem) {
-#pragma clang fp contract(off)
   static_assert(sizeof(TOut) == 2, "paired epilogue: 16-bit storage");
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   TOut* __restrict__ yg = reinterpret_cast<TOut*>(p.y);
   const TOut* __restrict__ rg = reinterpret_cast<const TOut*>(p.res);
   const TOut* __restrict__ vg = reinterpret_cast<const TOut*>(p.pair_v);
   TOut* __restrict__ ng = reinterpret_cast<TOut*>(p.ln_out);
   float* T = reinterpret_cast<float*>(smem);
-  const bool has_ln = p.ln_mode != 0;                    // uniform
   const float alpha = 1.0f / (1.0f + __expf(-p.mix_factor[0]));
   constexpr int RS = 16;
   const int j = tid & 31, rsub = tid >> 5;
@@ -488,53 +351,14 @@ __device__ __forceinline__ void conv_epilogue_lds256_pair(const ConvArgs& p, f32
   const bool has_prev = frame != fast_div(frame, p.fd_to) * (unsigned)p.To;      // t > 0: V[j-1] exists
   const long long row0 = (long long)frame * hw;                                  // output row of pixel m, frame 2j: m + frame * hw
   f32x2 lg[4], lb[4];
-  if (has_ln) {
-    const f32x4 g0 = *reinterpret_cast<const f32x4*>(p.ln_gamma + 8 * j), g1 = *reinterpret_cast<const f32x4*>(p.ln_gamma + 8 * j + 4);
-    const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.ln_beta + 8 * j), b1 = *reinterpret_cast<const f32x4*>(p.ln_beta + 8 * j + 4);
-    lg[0] = f32x2{g0[0], g0[1]}; lg[1] = f32x2{g0[2], g0[3]}; lg[2] = f32x2{g1[0], g1[1]}; lg[3] = f32x2{g1[2], g1[3]};
-    lb[0] = f32x2{b0[0], b0[1]}; lb[1] = f32x2{b0[2], b0[3]}; lb[2] = f32x2{b1[0], b1[1]}; lb[3] = f32x2{b1[2], b1[3]};
-    if (p.ln_mode == 2) {                                  // SiLU: the affine carries -log2(e) (ln_row8, common.h)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        lg[q] = lg[q] * kNegLog2e;
-        lb[q] = lb[q] * kNegLog2e;
-      }
-    }
-  }
-  // one output row: the mix against x[j], the store, the LayerNorm of the unrounded row (one-pass form, as conv_epilogue_lds256)
+  if (p.ln_mode) rows_affine(p, j, p.ln_mode == 2, lg, lb);
+  // one output row: t + V, then the mix against x[j], the store and the LayerNorm of the unrounded row
   auto emit = [&](const f32x2 (&t)[4], const Oct<TOut>& vq, const Oct<TOut>& xq, long long orow) {
     f32x2 v[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      v[q] = t[q] + f32x2{vq.get(2 * q), vq.get(2 * q + 1)};
-      v[q] = f32x2{xq.get(2 * q), xq.get(2 * q + 1)} * alpha + v[q] * (1.0f - alpha);
-    }
-    if (p.ln_keep_y || !has_ln) {
-      const float yv[8] = {v[0][0], v[0][1], v[1][0], v[1][1], v[2][0], v[2][1], v[3][0], v[3][1]};
-      Oct<TOut>::store(yg + orow * p.ldy + n_blk + 8 * j, yv, p.nt_store != 0);
-    }
-    if (!has_ln) return;
-    float o[8];
-    const f32x2 s = (v[0] + v[1]) + (v[2] + v[3]);
-    f32x2 qq = v[0] * v[0];
-#pragma unroll
-    for (int q = 1; q < 4; ++q) qq = __builtin_elementwise_fma(v[q], v[q], qq);
-    float nm;
-    const float rstd = ln_row_stats<32>(s[0] + s[1], qq[0] + qq[1], p.ln_eps, &nm);
-    const f32x2 rstd2 = {rstd, rstd}, nm2 = {nm, nm}, c2 = {kNegLog2e, kNegLog2e};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      f32x2 u = __builtin_elementwise_fma(__builtin_elementwise_fma(v[q], rstd2, nm2), lg[q], lb[q]);
-      if (p.ln_mode == 2) {
-        const f32x2 den = __builtin_elementwise_fma(f32x2{__builtin_amdgcn_exp2f(u[0]), __builtin_amdgcn_exp2f(u[1])}, c2, c2);
-        u = u * f32x2{__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-      }
-      o[2 * q] = u[0];
-      o[2 * q + 1] = u[1];
-    }
-    Oct<TOut>::store(ng + orow * p.ldn + 8 * j, o, p.nt_store != 0);
+    for (int q = 0; q < 4; ++q) v[q] = t[q] + f32x2{vq.get(2 * q), vq.get(2 * q + 1)};
+    rows_finish<32, TOut, 0>(p, VT_RES_MIX, v, xq, alpha, lg, lb, yg + orow * p.ldy + n_blk + 8 * j, ng + orow * p.ldn + 8 * j);
   };
-  const int h = lane >> 5;
   auto half = [&](auto pz_c) {
     constexpr int PZ = decltype(pz_c)::value;            // compile-time: acc[.][PZ] must not become a dynamic register index
     // tile pixel of T row r = rsub + RS it:  (r >> 5) * 64 + PZ * 32 + (r & 31)
@@ -545,22 +369,7 @@ __device__ __forceinline__ void conv_epilogue_lds256_pair(const ConvArgs& p, f32
       xq[it].load(rg + m * p.ldr + n_blk + 8 * j);
     }
     __syncthreads();                                    // K loop / previous half: everybody is done with this LDS
-    {
-      const int prl = wm * 32 + (lane & 31);
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int c = wn * 128 + 32 * a + 8 * g + 4 * h;
-          f32x4 bq;
-          if (p.bias) bq = *reinterpret_cast<const f32x4*>(p.bias + n_blk + c);
-          else bq[0] = bq[1] = bq[2] = bq[3] = 0.0f;
-          f32x4 v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = acc[a][PZ][4 * g + e] + bq[e];
-          *reinterpret_cast<f32x4*>(T + prl * 256 + (((c >> 2) ^ (prl & 63)) << 2)) = v;
-        }
-    }
+    lds256_scatter_half<PZ>(p, acc, T, n_blk, wm, wn, lane);
     __syncthreads();
     Oct<TOut> vp[4], vc[4];                              // V[j-1], V[j] of four rows
 #pragma unroll
@@ -574,11 +383,9 @@ __device__ __forceinline__ void conv_epilogue_lds256_pair(const ConvArgs& p, f32
           else vp[k].w = u32x4{0u, 0u, 0u, 0u};
         }
       }
-      const int r = rsub + RS * it;
       const long long m = (long long)m_blk + ((RS * it) >> 5) * 64 + PZ * 32 + rsub + ((RS * it) & 31);
-      const f32x4 t0 = *reinterpret_cast<const f32x4*>(T + r * 256 + (((2 * j) ^ (r & 63)) << 2));
-      const f32x4 t1 = *reinterpret_cast<const f32x4*>(T + r * 256 + (((2 * j + 1) ^ (r & 63)) << 2));
-      const f32x2 t[4] = {f32x2{t0[0], t0[1]}, f32x2{t0[2], t0[3]}, f32x2{t1[0], t1[1]}, f32x2{t1[2], t1[3]}};
+      f32x2 t[4];
+      rows_read<256>(T, rsub + RS * it, j, t);
       emit(t, vp[it & 3], xq[it], m + row0);
       emit(t, vc[it & 3], xq[it], m + row0 + hw);
     }

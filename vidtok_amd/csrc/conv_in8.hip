@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "conv_select.h"
+#include "conv_rows.h"
 
 namespace {
 
@@ -32,82 +33,37 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 constexpr int kIn8TBytes = 64 * 128 * 4;      // the epilogue's 64-row transposition buffer
 
-// conv_epilogue_lds128's row phase for a 1 x 4 wave grid (a wave: channels [32 wave, +32) of all 128 pixels), through a 64-row buffer in
-// two passes (pixel fragments 0, 1 then 2, 3).  The transposition layout and the row arithmetic are conv_epilogue_lds128's, statement
-// for statement: the bits must not depend on which kernel produced a pixel.
+// The 128-wide row phase of conv_rows.h (scalar rows, as conv_epilogue_lds128_at: the bits must not depend on which kernel produced a
+// pixel) for a 1 x 4 wave grid (a wave: channels [32 wave, +32) of all 128 pixels), through a 64-row buffer in two passes (pixel
+// fragments 0, 1 then 2, 3): 4 rows a lane per pass, no residual.
 template <typename TOut>
 __device__ __forceinline__ void conv_epilogue_in8(const ConvArgs& p, f32x16 (&acc)[4], int m_blk, int wave, int lane, int tid, char* smem) {
+  static_assert(sizeof(TOut) == 2, "conv_in8_kernel: 16-bit storage");
   TOut* __restrict__ yg = reinterpret_cast<TOut*>(p.y);
   TOut* __restrict__ ng = reinterpret_cast<TOut*>(p.ln_out);
   float* T = reinterpret_cast<float*>(smem);
   const int oct_j = tid & 15;
   const int row0 = tid >> 4;
   float lg[8], lb[8];
-  if (p.ln_mode) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      lg[e] = ln_fold(p.ln_gamma[8 * oct_j + e], sizeof(TOut) == 2 && p.ln_mode == 2);     // 16-bit storage + SiLU: the affine carries -log2(e)
-      lb[e] = ln_fold(p.ln_beta[8 * oct_j + e], sizeof(TOut) == 2 && p.ln_mode == 2);
-    }
-  }
+  if (p.ln_mode) rows_affine(p, oct_j, p.ln_mode == 2, lg, lb);
   static_for<0, 2>([&](auto pc) __attribute__((always_inline)) {
     constexpr int pass = decltype(pc)::value;
     __syncthreads();                            // the patch reads / the previous pass's rows are done
-    {
-      const int h = lane >> 5;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int c = 32 * wave + 8 * g + 4 * h;               // first channel of the quad
-        f32x4 bq;
-        if (p.bias) bq = *reinterpret_cast<const f32x4*>(p.bias + c);
-        else bq[0] = bq[1] = bq[2] = bq[3] = 0.0f;
+    for (int g = 0; g < 4; ++g) {
+      const int c = 32 * wave + 8 * g + 4 * (lane >> 5);       // first channel of the quad
+      const f32x4 bq = rows_bias(p.bias, c);
 #pragma unroll
-        for (int bl = 0; bl < 2; ++bl) {
-          const int prow = bl * 32 + (lane & 31);
-          f32x4 v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = acc[2 * pass + bl][4 * g + e] + bq[e];
-          *reinterpret_cast<f32x4*>(T + prow * 128 + (((c >> 2) ^ (prow & 31)) << 2)) = v;
-        }
-      }
+      for (int bl = 0; bl < 2; ++bl) rows_scatter<128>(T, bl * 32 + (lane & 31), c, acc[2 * pass + bl], g, bq);
     }
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int row = row0 + 16 * it;
-      const int sw = row & 31;
-      const f32x4 t0 = *reinterpret_cast<const f32x4*>(T + row * 128 + (((2 * oct_j) ^ sw) << 2));
-      const f32x4 t1 = *reinterpret_cast<const f32x4*>(T + row * 128 + (((2 * oct_j + 1) ^ sw) << 2));
       float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = e < 4 ? t0[e] : t1[e - 4];
+      rows_read<128>(T, row, oct_j, v);
       const long long orow = out_row(p, m_blk + 64 * pass + row);
-      if (!p.ln_mode || p.ln_keep_y) Oct<TOut>::store(yg + orow * p.ldy + 8 * oct_j, v, p.nt_store != 0);
-      if (p.ln_mode) {   // uniform; statistics of the fp32 row, taken before the rounding to TOut
-        float o[8];
-        if constexpr (sizeof(TOut) == 2) {   // 16-bit storage: the one-pass form every fused LayerNorm site of these modes shares (ln_row8, common.h; lg / lb folded above)
-          if (p.ln_mode == 2) ln_row8<16, true>(v, lg, lb, p.ln_eps, o);
-          else ln_row8<16, false>(v, lg, lb, p.ln_eps, o);
-        } else {                              // fp32 storage (fp32 / split-bf16 modes): two-pass statistics like layernorm_act_kernel
-          float s = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) s += v[e];
-          const float mean = group_sum_dpp<16>(s) * (1.0f / 128.0f);
-          float q = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            v[e] -= mean;
-            q += v[e] * v[e];
-          }
-          const float rstd = __builtin_amdgcn_rsqf(group_sum_dpp<16>(q) * (1.0f / 128.0f) + p.ln_eps);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float u = v[e] * rstd * lg[e] + lb[e];
-            o[e] = (p.ln_mode == 2) ? silu_fast(u) : u;
-          }
-        }
-        Oct<TOut>::store(ng + orow * p.ldn + 8 * oct_j, o, p.nt_store != 0);
-      }
+      rows_finish<16, TOut, 0>(p, VT_RES_NONE, v, Oct<TOut>{}, 0.0f, lg, lb, yg + orow * p.ldy + 8 * oct_j, ng + orow * p.ldn + 8 * oct_j);
     }
   });
 }

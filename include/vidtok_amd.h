@@ -846,6 +846,64 @@ int vt_grad_ncthw_to_ndhwc(const float* x, void* y, int32_t out_dtype, int32_t B
                            int32_t ldy, int32_t tpad, vt_stream stream);
 int vt_grad_add(const void* a, const void* b, void* out, int32_t dtype, int64_t n, vt_stream stream);
 
+/* ---- PatchGAN discriminator (reference vidtok/modules/discriminator.py:88-137, the adversarial term of losses.py:187-249) -----------
+ * NLayerDiscriminator is Conv2d k4 (s2, s2, s2, s1, s1) with BatchNorm2d + LeakyReLU(0.2) between; its convolutions are vt_conv, its
+ * weight gradients vt_conv_wgrad, its stride-1 data gradients vt_conv_dgrad.  The entry points below are the rest.  All take VT_F32 /
+ * VT_BF16 (VT_ERR_ARG otherwise, fp16 included: there is no loss scaling here), compute in fp32, use no float atomics, reduce over rows
+ * through per-workgroup partials in the caller's `work` added in index order by a second launch (bit-reproducible), neither allocate
+ * nor synchronise (capture-safe on `stream`), and write zeros into the pad lanes C..ld-1 of every row they own.  Rows are the M pixels
+ * of an NDHWC tensor, row strides multiples of 8, C <= 512, tensors 16-byte aligned.
+ *
+ * vt_batchnorm_stats: mean[c] and the BIASED variance var[c] over the M rows of x [M][ld], fp32 [C]; rstd[c] = 1 / sqrt(var[c] + eps)
+ *   as well where rstd != NULL.  The partial sums of x and x^2 are fp64 (work: vt_batchnorm_stats_work_bytes(M, C) bytes, -1 for
+ *   C > 512), so a mean far from zero costs no digits of the variance.
+ * vt_batchnorm_act: y = leaky(gamma[c] (x - mean[c]) rstd[c] + beta[c]), leaky(v) = v > 0 ? v : slope v.  The batch statistics of
+ *   vt_batchnorm_stats (train mode), the running statistics (eval mode), or mean 0 / rstd 1 / gamma 1 / beta 0: a plain LeakyReLU,
+ *   bit-exact (the discriminator's first layer).
+ * vt_batchnorm_act_backward: x the saved convolution output, dy dL/dy (dy_dtype: dtype or VT_F32).  With pre the forward's
+ *   pre-activation, recomputed by the same device expression (so the mask is the forward's bit for bit; pre == 0 takes `slope`, as
+ *   torch), g = dy (pre > 0 ? 1 : slope) and x^ = (x - mean) rstd:
+ *     dbeta[c] = sum g, dgamma[c] = sum g x^      (fp32 [C]; either may be NULL)
+ *     mode VT_BN_BATCH:   dx = gamma rstd (g - sum g / M - x^ sum(g x^) / M)
+ *     mode VT_BN_RUNNING: dx = gamma rstd g       (mean / rstd are constants of the call)
+ *   dx in dtype, rounded once.  work: vt_batchnorm_act_backward_work_bytes(M, C) bytes.
+ * vt_leaky_relu_backward: dx[i] = dy[i] (y[i] > 0 ? 1 : slope) for i < n (n a multiple of 8) from the saved POST-activation y -- the
+ *   sign of y is the sign of the pre-activation because slope > 0 (slope <= 0 is refused); dy in dy_dtype (dtype or VT_F32), dx in
+ *   dtype.  Bit-exact.
+ *
+ * vt_conv_dgrad_strided: the data gradient of a vt_conv with row and / or column stride 2, on the descriptor of vt_conv_dgrad (which
+ *   keeps refusing strides): st = 1, sh and sw in {1, 2} with at least one 2, tmode VT_TPAD_ZERO, no ups, KT, KH, KW <= 4, the pads of
+ *   the descriptor, dy extents the forward's ((Hi + ph + ph_hi - KH) / sh + 1).  An input pixel of parity class (rh, rw) = (h mod sh,
+ *   w mod sw) receives only the taps k with (r + p - k) mod s = 0: per class, dx is a stride-1 convolution of dy with the flipped,
+ *   transposed sub-kernel of those taps under the front pad nk - 1 - (r + p) / s (k4 s2 p1: four 2 x 2 kernels, 16 tap products per 4
+ *   pixels; no zero-dilated dy).  The classes run on vt_conv unchanged, fp32 into `work` (vt_conv_dgrad_strided_work_bytes(d) bytes,
+ *   -1 = invalid descriptor); a finishing kernel interleaves them, adds acc and rounds ONCE to dx_dtype, pad lanes zero: the contract of
+ *   vt_conv_dgrad.  A class no tap reaches (K < s) is zeros.  Refused: pads that would put a class convolution in front of dy's first
+ *   pixel (nk - 1 < (r + p) / s).
+ * vt_pack_conv_weight_dgrad_strided: weight fp32 [Cout][Cin][KT][KH][KW] -> sh * sw blocks [Cin][ldw], block rh * sw + rw holding the
+ *   class's taps flipped (k = ((a' nkh + p') nkw + q') cout_p + co <- w[co][ci][KT-1-a'][kh0 + sh (nkh-1-p')][kw0 + sw (nkw-1-q')]),
+ *   zeros elsewhere; ldw >= KT ceil(KH / sh) ceil(KW / sw) cout_p, the same for every block.
+ * ---------------------------------------------------------------------------------------------------------------------- */
+#define VT_BN_BATCH 0
+#define VT_BN_RUNNING 1
+int64_t vt_batchnorm_stats_work_bytes(int64_t M, int32_t C);
+int vt_batchnorm_stats(const void* x, int32_t dtype, int64_t ld, int64_t M, int32_t C, float eps, float* mean, float* var, float* rstd,
+                       void* work, int64_t work_bytes, vt_stream stream);
+int vt_batchnorm_act(const void* x, int32_t dtype, int64_t ld, void* y, int64_t ldy, const float* mean, const float* rstd,
+                     const float* gamma, const float* beta, float slope, int64_t M, int32_t C, vt_stream stream);
+int64_t vt_batchnorm_act_backward_work_bytes(int64_t M, int32_t C);
+int vt_batchnorm_act_backward(const void* x, const void* dy, int32_t dtype, int32_t dy_dtype, int64_t ld, int64_t lddy, void* dx,
+                              int64_t ldo, const float* mean, const float* rstd, const float* gamma, const float* beta, float slope,
+                              float* dgamma, float* dbeta, int64_t M, int32_t C, int32_t mode, void* work, int64_t work_bytes,
+                              vt_stream stream);
+int vt_leaky_relu_backward(const void* dy, int32_t dy_dtype, const void* y, void* dx, int32_t dtype, int64_t n, float slope,
+                           vt_stream stream);
+int vt_pack_conv_weight_dgrad_strided(const float* w, void* out, int32_t out_dtype, int32_t Cout, int32_t Cin, int32_t cout_p,
+                                      int32_t KT, int32_t KH, int32_t KW, int32_t sh, int32_t sw, int32_t ph, int32_t pw, int64_t ldw,
+                                      vt_stream stream);
+int64_t vt_conv_dgrad_strided_work_bytes(const vt_dgrad_desc* d);
+int vt_conv_dgrad_strided(const vt_dgrad_desc* d, vt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ VT_GN_FRAME, VT_GN_PIXEL, VT_GN_CLIP = 0, 1, 2
 VT_RES_NONE, VT_RES_ADD, VT_RES_MIX = 0, 1, 2
 VT_NDHWC, VT_NCTHW = 0, 1
 VT_ACT_RELU = 1
+VT_BN_BATCH, VT_BN_RUNNING = 0, 1
 VT_LPIPS_CLAMP_Y, VT_LPIPS_ROUNDTRIP, VT_LPIPS_UNIT = 1, 2, 4
 VT_SESSION_ENCODE, VT_SESSION_DECODE = 0, 1
 
@@ -226,6 +227,15 @@ SIGNATURES = {
     "vt_time_lerp2x_backward": (C.c_int, [_P, _P, _I32, _I32, _I32, _I64, _P]),
     "vt_grad_ncthw_to_ndhwc": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "vt_grad_add": (C.c_int, [_P, _P, _P, _I32, _I64, _P]),
+    "vt_batchnorm_stats_work_bytes": (_I64, [_I64, _I32]),
+    "vt_batchnorm_stats": (C.c_int, [_P, _I32, _I64, _I64, _I32, _F, _P, _P, _P, _P, _I64, _P]),
+    "vt_batchnorm_act": (C.c_int, [_P, _I32, _I64, _P, _I64, _P, _P, _P, _P, _F, _I64, _I32, _P]),
+    "vt_batchnorm_act_backward_work_bytes": (_I64, [_I64, _I32]),
+    "vt_batchnorm_act_backward": (C.c_int, [_P, _P, _I32, _I32, _I64, _I64, _P, _I64, _P, _P, _P, _P, _F, _P, _P, _I64, _I32, _I32, _P, _I64, _P]),
+    "vt_leaky_relu_backward": (C.c_int, [_P, _I32, _P, _P, _I32, _I64, _F, _P]),
+    "vt_pack_conv_weight_dgrad_strided": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _P]),
+    "vt_conv_dgrad_strided_work_bytes": (_I64, [C.POINTER(DgradDesc)]),
+    "vt_conv_dgrad_strided": (C.c_int, [C.POINTER(DgradDesc), _P]),
 }
 
 _lib = None

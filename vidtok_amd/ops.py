@@ -1226,3 +1226,128 @@ def lpips_prep_backward(d, scale):
     out = torch.empty((N, 3, H, W), dtype=torch.float32, device=d.device)
     L.check(lib.vt_lpips_prep_backward(_ptr(d), _DT[d.dtype], _ptr(scale), _ptr(out), N, H, W, _stream()), "vt_lpips_prep_backward")
     return out
+
+
+# ---- PatchGAN discriminator (include/vidtok_amd.h: vt_batchnorm_*, vt_leaky_relu_backward, vt_conv_dgrad_strided) ----------------------
+def batchnorm_stats(x, c: int = None, eps: float = 1e-5):
+    """vt_batchnorm_stats over the rows of x [..., ld] (fp32 or bf16): (mean, biased var, rstd = 1 / sqrt(var + eps)), fp32 [c] each"""
+    lib = L.load()
+    _chk(x, "batchnorm_stats.x")
+    assert x.dtype in _GRAD_DT, x.dtype
+    ld = x.shape[-1]
+    c = c or ld
+    M = x.numel() // ld
+    nb = lib.vt_batchnorm_stats_work_bytes(M, c)
+    if nb < 0:
+        raise L.VtError(f"vt_batchnorm_stats: unsupported size (M={M}, C={c}; C <= 512)")
+    work = torch.empty((nb,), dtype=torch.uint8, device=x.device)
+    mean, var, rstd = (torch.empty((c,), dtype=torch.float32, device=x.device) for _ in range(3))
+    L.check(lib.vt_batchnorm_stats(_ptr(x), _DT[x.dtype], ld, M, c, float(eps), _ptr(mean), _ptr(var), _ptr(rstd), _ptr(work), nb, _stream()),
+            "vt_batchnorm_stats")
+    return mean, var, rstd
+
+
+def _chan(t, c, name):
+    assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() >= c, (name, t.dtype, t.shape)
+
+
+def batchnorm_act(x, mean, rstd, gamma, beta, slope: float, c: int = None):
+    """vt_batchnorm_act: y = leaky(gamma (x - mean) rstd + beta, slope) per channel over the rows of x [..., ld], in x's dtype, pad lanes zero"""
+    lib = L.load()
+    _chk(x, "batchnorm_act.x")
+    assert x.dtype in _GRAD_DT, x.dtype
+    ld = x.shape[-1]
+    c = c or ld
+    for n, t in (("mean", mean), ("rstd", rstd), ("gamma", gamma), ("beta", beta)):
+        _chan(t, c, n)
+    y = torch.empty_like(x)
+    L.check(lib.vt_batchnorm_act(_ptr(x), _DT[x.dtype], ld, _ptr(y), ld, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), float(slope), x.numel() // ld, c,
+                                 _stream()), "vt_batchnorm_act")
+    return y
+
+
+def batchnorm_act_backward(x, dy, mean, rstd, gamma, beta, slope: float, *, batch: bool, c: int = None, need_dgamma=True, need_dbeta=True):
+    """vt_batchnorm_act_backward: x the saved convolution output [..., ld], dy the gradient at the post-activation (x's dtype or fp32)
+    -> (dx in x's dtype, dgamma fp32 [c] or None, dbeta fp32 [c] or None); batch=True differentiates through the batch statistics"""
+    lib = L.load()
+    _chk(x, "batchnorm_act_backward.x"); _chk(dy, "batchnorm_act_backward.dy")
+    assert x.dtype in _GRAD_DT and dy.dtype in (x.dtype, torch.float32) and dy.shape == x.shape, (x.dtype, dy.dtype, tuple(x.shape), tuple(dy.shape))
+    ld = x.shape[-1]
+    c = c or ld
+    M = x.numel() // ld
+    for n, t in (("mean", mean), ("rstd", rstd), ("gamma", gamma), ("beta", beta)):
+        _chan(t, c, n)
+    nb = lib.vt_batchnorm_act_backward_work_bytes(M, c)
+    if nb < 0:
+        raise L.VtError(f"vt_batchnorm_act_backward: unsupported size (M={M}, C={c}; C <= 512)")
+    work = torch.empty((nb,), dtype=torch.uint8, device=x.device)
+    dx = torch.empty_like(x)
+    dg = torch.empty((c,), dtype=torch.float32, device=x.device) if need_dgamma else None
+    db = torch.empty((c,), dtype=torch.float32, device=x.device) if need_dbeta else None
+    L.check(lib.vt_batchnorm_act_backward(_ptr(x), _ptr(dy), _DT[x.dtype], _DT[dy.dtype], ld, ld, _ptr(dx), ld, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
+                                          float(slope), _ptr(dg), _ptr(db), M, c, L.VT_BN_BATCH if batch else L.VT_BN_RUNNING, _ptr(work), nb, _stream()),
+            "vt_batchnorm_act_backward")
+    return dx, dg, db
+
+
+def leaky_relu_backward(dy, y, slope: float):
+    """vt_leaky_relu_backward: dy * (y > 0 ? 1 : slope) in y's dtype; y the saved post-activation, dy in y's dtype or fp32 (rounded once)"""
+    lib = L.load()
+    _chk(dy, "leaky_relu_backward.dy"); _chk(y, "leaky_relu_backward.y")
+    assert dy.shape == y.shape and y.dtype in _GRAD_DT and dy.dtype in (y.dtype, torch.float32), (tuple(dy.shape), tuple(y.shape), dy.dtype, y.dtype)
+    dx = torch.empty_like(y)
+    L.check(lib.vt_leaky_relu_backward(_ptr(dy), _DT[dy.dtype], _ptr(y), _ptr(dx), _DT[y.dtype], y.numel(), float(slope), _stream()), "vt_leaky_relu_backward")
+    return dx
+
+
+def pack_conv_weight_dgrad_strided(weight, dtype, geom: ConvGeom, cout_stored=None):
+    """vt_pack_conv_weight_dgrad_strided: weight fp32 [Cout, Cin, *k] on the GPU -> [sh * sw, Cin, ldw]: per parity class of the input the
+    flipped, transposed sub-kernel vt_conv_dgrad_strided convolves dy with (packing.strided_dgrad_classes)"""
+    lib = L.load()
+    _chk(weight, "pack_dgrad_strided.weight")
+    assert weight.dtype == torch.float32 and weight.dim() in (4, 5) and dtype in _GRAD_DT
+    cout, cin = weight.shape[:2]
+    kt, kh, kw = (1,) * (5 - weight.dim()) + tuple(weight.shape[2:])
+    assert (kt, kh, kw) == (geom.kt, geom.kh, geom.kw), ((kt, kh, kw), geom)
+    cout_p = cout_stored or pad_channels(cout)
+    ldw = kt * -(-kh // geom.sh) * -(-kw // geom.sw) * cout_p
+    out = torch.empty((geom.sh * geom.sw, cin, ldw), dtype=dtype, device=weight.device)
+    L.check(lib.vt_pack_conv_weight_dgrad_strided(_ptr(weight), _ptr(out), _DT[dtype], cout, cin, cout_p, kt, kh, kw, geom.sh, geom.sw, geom.ph, geom.pw, ldw,
+                                                  _stream()), "vt_pack_conv_weight_dgrad_strided")
+    return out
+
+
+def conv_dgrad_strided(dy, w, geom: ConvGeom, *, cin: int, cout: int, in_hw, acc=None, dx_dtype=None):
+    """dx of `conv(x, ..., geom, cout=cout)` with row / column stride 2 with respect to its stored input x [B, Ti, in_hw[0], in_hw[1],
+    pad_channels(cin)]: dy [B, To, Ho, Wo, >= cout] fp32 or bf16, w = pack_conv_weight_dgrad_strided(weight, dy.dtype, geom, dy.shape[-1]).
+    in_hw: the forward input's (Hi, Wi) -- a strided output extent does not determine them.  acc / dx_dtype as conv_dgrad."""
+    lib = L.load()
+    _chk(dy, "conv_dgrad_strided.dy"); _chk(w, "conv_dgrad_strided.w")
+    assert dy.dtype in _GRAD_DT and w.dtype == dy.dtype and dy.dim() == 5 and w.dim() == 3, (dy.dtype, w.dtype)
+    dx_dtype = dx_dtype or dy.dtype
+    B, To, Ho, Wo, lddy = dy.shape
+    Hi, Wi = in_hw
+    Ti = To - geom.pt - geom.pt_hi + geom.kt - 1
+    ldx = pad_channels(cin)
+    d = L.DgradDesc()
+    d.dy, d.wt = dy.data_ptr(), w.data_ptr()
+    d.B, d.Ti, d.Hi, d.Wi, d.lddx, d.Cin = B, Ti, Hi, Wi, ldx, cin
+    d.To, d.Ho, d.Wo, d.lddy, d.Cout = To, Ho, Wo, lddy, cout
+    d.KT, d.KH, d.KW, d.st, d.sh, d.sw = geom.kt, geom.kh, geom.kw, geom.st, geom.sh, geom.sw
+    d.pt, d.ph, d.pw, d.pt_hi, d.ph_hi, d.pw_hi = geom.pt, geom.ph, geom.pw, geom.pt_hi, geom.ph_hi, geom.pw_hi
+    d.tmode, d.ups_t, d.ups_s, d.dtype, d.dx_dtype = L.VT_TPAD_ZERO, geom.ups_t, geom.ups_s, _DT[dy.dtype], _DT.get(dx_dtype, -1)
+    d.ldw = w.shape[2]
+    if acc is not None:
+        _chk(acc, "conv_dgrad_strided.acc")
+        assert acc.dtype == dx_dtype and tuple(acc.shape) == (B, Ti, Hi, Wi, ldx), (acc.dtype, tuple(acc.shape))
+        d.acc, d.ldacc = acc.data_ptr(), ldx
+    nb = lib.vt_conv_dgrad_strided_work_bytes(C.byref(d))
+    if nb < 0:
+        L.check(-1, "vt_conv_dgrad_strided_work_bytes")
+    assert tuple(w.shape[:2]) == (geom.sh * geom.sw, cin), (tuple(w.shape), cin)
+    dx = torch.empty((B, Ti, Hi, Wi, ldx), dtype=dx_dtype, device=dy.device)
+    d.dx = dx.data_ptr()
+    work = torch.empty((max(nb, 16),), dtype=torch.uint8, device=dy.device)
+    d.work, d.work_bytes = work.data_ptr(), nb
+    L.check(lib.vt_conv_dgrad_strided(C.byref(d), _stream()), "vt_conv_dgrad_strided")
+    return dx

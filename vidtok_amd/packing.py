@@ -233,3 +233,24 @@ class ConvSite:
         if self._dgrad is None:
             self._dgrad = DgradPackCache()
         return self._dgrad.get(self.conv.weight, dtype, cout_stored)
+
+
+# ---- parity classes of a strided convolution's data gradient (vt_conv_dgrad_strided, include/vidtok_amd.h) ----------------------------
+def strided_axis_class(k: int, s: int, p: int, r: int, extent: int = None) -> dict:
+    """one axis of a parity class: input positions i = s j + r receive the taps k0, k0 + s, ... (those with (r + p - tap) mod s = 0)
+    from dy[j + (r + p) // s - m] for the m-th of them.  As a stride-1 convolution over dy that is the flipped tap list under the front
+    pad nk - 1 - (r + p) // s.  -> dict(r, taps (forward tap indices in flipped order, as the class kernel walks them), pad, n (class
+    extent, with `extent`))"""
+    k0 = (r + p) % s
+    taps = list(range(k0, k, s))
+    out = dict(r=r, taps=taps[::-1], pad=len(taps) - 1 - (r + p) // s)
+    if extent is not None:
+        out["n"] = (extent - r + s - 1) // s if extent > r else 0
+    return out
+
+
+def strided_dgrad_classes(kh: int, kw: int, sh: int, sw: int, ph: int, pw: int, hi: int = None, wi: int = None) -> list:
+    """the class table of vt_conv_dgrad_strided, class rh * sw + rw at index rh * sw + rw: [(rows, cols)] of strided_axis_class.  Every
+    forward tap (p, q) appears in exactly one class; a class with an empty tap list is zeros; a negative pad is a geometry the entry
+    point refuses."""
+    return [(strided_axis_class(kh, sh, ph, rh, hi), strided_axis_class(kw, sw, pw, rw, wi)) for rh in range(sh) for rw in range(sw)]

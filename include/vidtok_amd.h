@@ -781,25 +781,34 @@ int vt_layernorm_act_backward(const void* y, const void* dn, int32_t dtype, int6
                               int32_t silu, void* work, int64_t work_bytes, vt_stream stream);
 
 /* ---- differentiable decode: the data-gradient path (decoder fine-tuning) ------------------------------------------------------
- * vt_conv_dgrad: dx = the gradient of a STRIDE-1 vt_conv with respect to its stored input x [B][Ti][Hi][Wi][lddx] (before a folded
- * nearest x2 up-sampling), from dy [B][To][Ho][Wo][lddy] (dtype VT_F32 / VT_BF16; pad lanes of dy may hold any finite value).  The
- * MACs run on vt_conv itself: dx over the virtual (up-sampled, padded) input is the convolution of dy with the weight packed by
- * vt_pack_conv_weight_dgrad (taps flipped, Cin / Cout transposed, rows of ldw >= taps * lddy with zero pad channels) under mirrored
- * pads (front pad K-1-p, back pad K-1-p_hi).  Plain geometries with fp32 dx are written by that launch (acc rides its residual
- * epilogue; lanes Cin..lddx-1 of dx are NOT written then: hand in a zeroed dx where they matter).  Otherwise the convolution writes
- * fp32 into `work` (vt_conv_dgrad_work_bytes(d) bytes; 0 = none needed, -1 = invalid descriptor) and a fold kernel finishes: under
+ * vt_conv_dgrad: dx = the gradient of a vt_conv with respect to its stored input x [B][Ti][Hi][Wi][lddx] (before a folded nearest x2
+ * up-sampling), from dy [B][To][Ho][Wo][lddy] (dtype VT_F32 / VT_BF16; pad lanes of dy may hold any finite value).  The MACs run on
+ * vt_conv itself.  An input pixel of parity class (rh, rw) = (h mod sh, w mod sw) receives only the taps k with (r + p - k) mod s = 0:
+ * per class, dx is a stride-1 convolution of dy with the flipped, transposed sub-kernel of those taps (vt_pack_conv_weight_dgrad)
+ * under the front pad nk - 1 - (r + p) / s.  Stride 1 is one class with every tap under the mirrored pads K-1-p; k4 s2 p1 is four
+ * 2 x 2 kernels, 16 tap products per 4 pixels, no zero-dilated dy; a class without a pixel (extent <= r) takes no launch.  A stride-1 geometry
+ * without replicate pad or ups and with fp32 dx is written by that one launch (acc rides its residual epilogue; lanes Cin..lddx-1 of
+ * dx are NOT written then: hand in a zeroed dx where they matter).  Otherwise the class convolutions write fp32 into `work`
+ * (vt_conv_dgrad_work_bytes(d) bytes; 0 = none needed, -1 = invalid descriptor; a lone class takes exactly its size, several classes
+ * a multiple of 256 bytes each) and one finishing launch reads them: an output pixel sums its virtual positions -- under
  * VT_TPAD_REPLICATE the pt virtual front frames add into frame 0, under ups_t / ups_s the 2 / 2 x 2 up-sampled positions add into
- * their source pixel, then acc (dx_dtype, row stride ldacc) is added and the fp32 sum is rounded ONCE to dx_dtype (dtype or VT_F32),
- * pad lanes zero.  A bf16 dx is therefore the rounded fp32 dx bit for bit.  No atomics; sums in a fixed order; capture-safe.
- * Strided geometries (st, sh or sw != 1) return VT_ERR_ARG with a message: the decoders have none (their only strided
- * convolutions are the encoder's down-samplers).  Also refused: tmode VT_TPAD_CACHE, pads >= the kernel extent, dy extents that
- * are not the forward convolution's.
- * vt_grad_fold: the finishing kernel on its own (src [B][rep + (T << ups_t)][H << ups_s][W << ups_s][lds], fp32 or dx_dtype) -- with
+ * their source pixel; under a stride it is the one position of the pixel's class -- then acc (dx_dtype, row stride ldacc) is added
+ * and the fp32 sum is rounded ONCE to dx_dtype (dtype or VT_F32), pad lanes zero.  A bf16 dx is therefore the rounded fp32 dx bit for bit.  No atomics; sums in a fixed
+ * order; capture-safe.
+ * Served: strides (1, 1, 1) with a zero or replicate time pad, ups_t / ups_s, up to 64 taps; st = 1 with sh, sw in {1, 2} and at
+ * least one 2 under VT_TPAD_ZERO without ups, KT, KH, KW <= 4, dy extents the forward's ((Hi + ph + ph_hi - KH) / sh + 1).  Everything
+ * else returns VT_ERR_ARG with a message: st != 1, stride 3, a stride with ups or a replicate pad, tmode VT_TPAD_CACHE, pads >= the
+ * kernel extent, pads that would put a class convolution in front of dy's first pixel (nk - 1 < (r + p) / s), dy extents that are
+ * not the forward convolution's.
+ * vt_pack_conv_weight_dgrad: weight fp32 [Cout][Cin][KT][KH][KW] -> sh * sw blocks [Cin][ldw], block rh * sw + rw holding the class's
+ * taps flipped (k = ((a' nkh + p') nkw + q') cout_p + co <- w[co][ci][KT-1-a'][kh0 + sh (nkh-1-p')][kw0 + sw (nkw-1-q')]), zeros
+ * elsewhere; ldw >= KT ceil(KH / sh) ceil(KW / sw) cout_p, the same for every block.  sh = sw = 1: one block, all taps flipped.
+ * vt_grad_fold: the finishing kernel of one class on its own (src [B][rep + (T << ups_t)][H << ups_s][W << ups_s][lds], fp32 or dx_dtype) -- with
  * rep = 0, ups_t = 1 it is the backward of a nearest x2 time up-sampling.
  * ---------------------------------------------------------------------------------------------------------------------- */
 typedef struct vt_dgrad_desc {
   const void* dy;
-  const void* wt;        /* vt_pack_conv_weight_dgrad rows [Cin][ldw] in `dtype` */
+  const void* wt;        /* vt_pack_conv_weight_dgrad blocks [sh * sw][Cin][ldw] in `dtype` */
   void* dx;
   const void* acc;       /* optional: a gradient already held for x, added (dx_dtype) */
   void* work;
@@ -813,7 +822,7 @@ typedef struct vt_dgrad_desc {
 } vt_dgrad_desc;
 int vt_dgrad_desc_size(void);
 int vt_pack_conv_weight_dgrad(const float* w, void* out, int32_t out_dtype, int32_t Cout, int32_t Cin, int32_t cout_p, int32_t KT,
-                              int32_t KH, int32_t KW, int64_t ldw, vt_stream stream);
+                              int32_t KH, int32_t KW, int32_t sh, int32_t sw, int32_t ph, int32_t pw, int64_t ldw, vt_stream stream);
 int64_t vt_conv_dgrad_work_bytes(const vt_dgrad_desc* d);
 int vt_conv_dgrad(const vt_dgrad_desc* d, vt_stream stream);
 int vt_grad_fold(const void* src, int32_t src_dtype, const void* acc, void* dx, int32_t dx_dtype, int32_t B, int32_t T, int32_t H, int32_t W, int32_t C,
@@ -848,7 +857,7 @@ int vt_grad_add(const void* a, const void* b, void* out, int32_t dtype, int64_t 
 
 /* ---- PatchGAN discriminator (reference vidtok/modules/discriminator.py:88-137, the adversarial term of losses.py:187-249) -----------
  * NLayerDiscriminator is Conv2d k4 (s2, s2, s2, s1, s1) with BatchNorm2d + LeakyReLU(0.2) between; its convolutions are vt_conv, its
- * weight gradients vt_conv_wgrad, its stride-1 data gradients vt_conv_dgrad.  The entry points below are the rest.  All take VT_F32 /
+ * weight gradients vt_conv_wgrad, its data gradients vt_conv_dgrad.  The entry points below are the rest.  All take VT_F32 /
  * VT_BF16 (VT_ERR_ARG otherwise, fp16 included: there is no loss scaling here), compute in fp32, use no float atomics, reduce over rows
  * through per-workgroup partials in the caller's `work` added in index order by a second launch (bit-reproducible), neither allocate
  * nor synchronise (capture-safe on `stream`), and write zeros into the pad lanes C..ld-1 of every row they own.  Rows are the M pixels
@@ -870,19 +879,6 @@ int vt_grad_add(const void* a, const void* b, void* out, int32_t dtype, int64_t 
  * vt_leaky_relu_backward: dx[i] = dy[i] (y[i] > 0 ? 1 : slope) for i < n (n a multiple of 8) from the saved POST-activation y -- the
  *   sign of y is the sign of the pre-activation because slope > 0 (slope <= 0 is refused); dy in dy_dtype (dtype or VT_F32), dx in
  *   dtype.  Bit-exact.
- *
- * vt_conv_dgrad_strided: the data gradient of a vt_conv with row and / or column stride 2, on the descriptor of vt_conv_dgrad (which
- *   keeps refusing strides): st = 1, sh and sw in {1, 2} with at least one 2, tmode VT_TPAD_ZERO, no ups, KT, KH, KW <= 4, the pads of
- *   the descriptor, dy extents the forward's ((Hi + ph + ph_hi - KH) / sh + 1).  An input pixel of parity class (rh, rw) = (h mod sh,
- *   w mod sw) receives only the taps k with (r + p - k) mod s = 0: per class, dx is a stride-1 convolution of dy with the flipped,
- *   transposed sub-kernel of those taps under the front pad nk - 1 - (r + p) / s (k4 s2 p1: four 2 x 2 kernels, 16 tap products per 4
- *   pixels; no zero-dilated dy).  The classes run on vt_conv unchanged, fp32 into `work` (vt_conv_dgrad_strided_work_bytes(d) bytes,
- *   -1 = invalid descriptor); a finishing kernel interleaves them, adds acc and rounds ONCE to dx_dtype, pad lanes zero: the contract of
- *   vt_conv_dgrad.  A class no tap reaches (K < s) is zeros.  Refused: pads that would put a class convolution in front of dy's first
- *   pixel (nk - 1 < (r + p) / s).
- * vt_pack_conv_weight_dgrad_strided: weight fp32 [Cout][Cin][KT][KH][KW] -> sh * sw blocks [Cin][ldw], block rh * sw + rw holding the
- *   class's taps flipped (k = ((a' nkh + p') nkw + q') cout_p + co <- w[co][ci][KT-1-a'][kh0 + sh (nkh-1-p')][kw0 + sw (nkw-1-q')]),
- *   zeros elsewhere; ldw >= KT ceil(KH / sh) ceil(KW / sw) cout_p, the same for every block.
  * ---------------------------------------------------------------------------------------------------------------------- */
 #define VT_BN_BATCH 0
 #define VT_BN_RUNNING 1
@@ -898,11 +894,6 @@ int vt_batchnorm_act_backward(const void* x, const void* dy, int32_t dtype, int3
                               vt_stream stream);
 int vt_leaky_relu_backward(const void* dy, int32_t dy_dtype, const void* y, void* dx, int32_t dtype, int64_t n, float slope,
                            vt_stream stream);
-int vt_pack_conv_weight_dgrad_strided(const float* w, void* out, int32_t out_dtype, int32_t Cout, int32_t Cin, int32_t cout_p,
-                                      int32_t KT, int32_t KH, int32_t KW, int32_t sh, int32_t sw, int32_t ph, int32_t pw, int64_t ldw,
-                                      vt_stream stream);
-int64_t vt_conv_dgrad_strided_work_bytes(const vt_dgrad_desc* d);
-int vt_conv_dgrad_strided(const vt_dgrad_desc* d, vt_stream stream);
 
 #ifdef __cplusplus
 }

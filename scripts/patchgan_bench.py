@@ -24,8 +24,8 @@ import patchgan_ref as R  # noqa: E402
 from vidtok_amd import ops  # noqa: E402
 from vidtok_amd.discriminator import NLayerDiscriminator  # noqa: E402
 
-OPS = ("ncthw_to_ndhwc", "conv", "batchnorm_stats", "batchnorm_act", "grad_ncthw_to_ndhwc", "conv_wgrad", "conv_dgrad", "conv_dgrad_strided",
-       "batchnorm_act_backward", "leaky_relu_backward", "ndhwc_to_ncthw")
+OPS = ("ncthw_to_ndhwc", "conv", "batchnorm_stats", "batchnorm_act", "grad_ncthw_to_ndhwc", "conv_wgrad", "conv_dgrad", "batchnorm_act_backward",
+       "leaky_relu_backward", "ndhwc_to_ncthw")
 
 
 def timed(fn, iters):

@@ -36,7 +36,9 @@ def test_c_surface():
         assert name + "(" in header, name
 
 
-def test_strided_geometry_is_refused_by_the_library():
+def test_strides_the_library_serves_and_refuses():
+    """vt_conv_dgrad serves st = 1 with sh, sw in {1, 2} (tests/test_patchgan_host.py::test_conv_dgrad_domain has the strided side); a
+    time stride and stride 3 are refused with a message, by the size query and by the launch"""
     from vidtok_amd import lib as L
 
     d = L.DgradDesc()
@@ -46,9 +48,12 @@ def test_strided_geometry_is_refused_by_the_library():
     d.ph_hi = d.pw_hi = 1
     d.ldw, d.dtype, d.dx_dtype = 72, L.VT_F32, L.VT_F32
     lib = L.load()
-    assert lib.vt_conv_dgrad_work_bytes(C.byref(d)) == -1 and b"stride" in lib.vt_last_error()
-    assert lib.vt_conv_dgrad(C.byref(d), None) != 0 and b"stride" in lib.vt_last_error()
-    d.sh = d.sw = 1                       # the same descriptor at stride 1 with matching extents is a plain launch: no workspace
+    assert lib.vt_conv_dgrad_work_bytes(C.byref(d)) == 4 * (1 * 1 * 4 * 4 * 8 * 4)         # four classes of 4 x 4 pixels, 512 bytes each
+    for st, sh in ((2, 2), (1, 3)):
+        d.st, d.sh = st, sh
+        assert lib.vt_conv_dgrad_work_bytes(C.byref(d)) == -1 and b"stride" in lib.vt_last_error()
+        assert lib.vt_conv_dgrad(C.byref(d), None) != 0 and b"stride" in lib.vt_last_error()
+    d.st = d.sh = d.sw = 1                # the same descriptor at stride 1 with matching extents is a plain launch: no workspace
     d.Ho = d.Wo = 7
     assert lib.vt_conv_dgrad_work_bytes(C.byref(d)) == 0
     d.dx_dtype, d.dtype = L.VT_BF16, L.VT_BF16      # a bf16 dx is rounded from an fp32 workspace

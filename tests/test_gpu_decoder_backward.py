@@ -140,6 +140,32 @@ def test_conv_dgrad_edge_grid():
     assert n_ok >= 2 * 13
 
 
+@pytest.mark.parametrize("out_dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("with_acc", [False, True], ids=["plain", "acc"])
+@pytest.mark.parametrize("ups", [(0, 0), (1, 0), (0, 1), (1, 1)], ids=["-", "t", "s", "ts"])
+@pytest.mark.parametrize("rep", [0, 2])
+def test_grad_fold_grid(rep, ups, with_acc, out_dtype):
+    """the finishing kernel of vt_conv_dgrad with one class (stride 1): every fold case bit-equal to torch_backward_ref.grad_fold on the
+    same fp32 source.  The kernel adds a pixel's positions frame by frame, the reference folds time first and space second: the source
+    holds multiples of 1/16 below 64 and acc integers below 256 (exact in bf16), so every partial sum of the at most 16 + 1 terms is exact
+    in fp32 in either order and the results are equal bits -- a wrong address, a lost term or a second rounding is not.  Pad lanes of the
+    source hold garbage; those of the result are zero"""
+    import torch_backward_ref as BR
+
+    ops, _ = _mods()
+    B, Tt, H, W, c, ld = 2, 3, 5, 6, 12, 16
+    ut, us = ups
+    gen = torch.Generator().manual_seed(100 * rep + 10 * ut + us)
+    src = torch.randint(-1023, 1024, (B, rep + (Tt << ut), H << us, W << us, ld), generator=gen).float() / 16
+    src[..., c:] = 7.0
+    acc = torch.randint(-255, 256, (B, Tt, H, W, ld), generator=gen).float().to(out_dtype) if with_acc else None
+    want = BR.grad_fold(src, ups_t=ut, ups_s=us, rep=rep, acc=acc, out_dtype=out_dtype)
+    got = ops.grad_fold(src.to(DEV), ups_t=ut, ups_s=us, rep=rep, c=c, acc=None if acc is None else acc.to(DEV), out_dtype=out_dtype)
+    assert got.dtype == out_dtype and tuple(got.shape) == (B, Tt, H, W, ld)
+    assert torch.equal(got.cpu()[..., :c], want[..., :c])
+    assert bool((got[..., c:] == 0).all())
+
+
 def test_softmax_rows_backward():
     ops, _ = _mods()
     gen = torch.Generator().manual_seed(1)

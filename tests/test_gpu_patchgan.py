@@ -1,6 +1,7 @@
 """PatchGAN discriminator on the GPU: the new kernels one by one against fp64 computed from the same stored operands, ops.conv_wgrad at
 the five layer geometries, arena runs of every new entry point, and the whole network (forward, both backward sides, the chain behind
 decode_with_grad) against fp64 autograd of the torch.nn restatement (tests/patchgan_ref.py)."""
+import dataclasses
 import functools
 
 import pytest
@@ -145,7 +146,7 @@ def test_leaky_relu_backward(dtype):
             assert dx.dtype == dtype and torch.equal(dx, want)
 
 
-# ---- 4. vt_conv_dgrad_strided -----------------------------------------------------------------------------------------------------------
+# ---- 4. vt_conv_dgrad under a row / column stride -------------------------------------------------------------------------------------------
 def _strided_geoms():
     from backward_sites import edge_geoms
     from vidtok_amd.ops import ConvGeom
@@ -154,7 +155,7 @@ def _strided_geoms():
             "1x3x3 s21": edge_geoms()["1x3x3 s21"][0]}
 
 
-def _ref_dgrad_strided(dy, w, g, cin, cout, x_shape):
+def _ref_strided_dx(dy, w, g, cin, cout, x_shape):
     B, T, H, W, _ = x_shape
     x = torch.zeros((B * T, cin, H, W), dtype=torch.float64, requires_grad=True)
     y = F.conv2d(F.pad(x, (g.pw, g.pw_hi, g.ph, g.ph_hi)), w.double(), stride=(g.sh, g.sw))
@@ -180,9 +181,9 @@ def test_conv_dgrad_strided(gname, dtype):
             dy = torch.randn((B, T, Ho, Wo, lddy), generator=_gen(12))
             dy[..., cout:] = 3.0
             dy = dy.to(dtype).to(DEV)
-            ref = _ref_dgrad_strided(dy, w, g, cin, cout, (B, T, H, W, ldx))
-            wt = ops.pack_conv_weight_dgrad_strided(w.float().to(DEV), dtype, g, lddy)
-            run = functools.partial(ops.conv_dgrad_strided, dy, wt, g, cin=cin, cout=cout, in_hw=(H, W))
+            ref = _ref_strided_dx(dy, w, g, cin, cout, (B, T, H, W, ldx))
+            wt = ops.pack_conv_weight_dgrad(w.float().to(DEV), dtype, lddy, g)
+            run = functools.partial(ops.conv_dgrad, dy, wt, g, cin=cin, cout=cout, in_hw=(H, W))
             dx = run(dx_dtype=F32)
             torch.cuda.synchronize()
             assert tuple(dx.shape) == (B, T, H, W, ldx) and dx.dtype == F32
@@ -202,16 +203,28 @@ def test_conv_dgrad_strided(gname, dtype):
                 assert torch.equal(dxha[..., :cin], (dx + acch.float()).to(BF16)[..., :cin])
 
 
-def test_conv_dgrad_refuses_strides_and_strided_refuses_stride_one():
+def test_conv_dgrad_domain_of_the_wrapper():
+    """ops.conv_dgrad on the GPU: a stride needs in_hw, what the library refuses raises with its message (host side of the domain:
+    tests/test_patchgan_host.py::test_conv_dgrad_domain), stride 1 checks an in_hw it is given"""
     ops, L = _mods()
     g = _strided_geoms()["k4 s2 p1"]
     dy = torch.zeros((1, 1, 4, 4, 8), device=DEV)
-    wt = ops.pack_conv_weight_dgrad_strided(torch.zeros((8, 8, 4, 4), device=DEV), F32, g, 8)
-    with pytest.raises(L.VtError, match="only stride-1 convolutions have a data gradient here"):
-        ops.conv_dgrad(dy, wt[0], g, cin=8, cout=8)
+    wt = ops.pack_conv_weight_dgrad(torch.zeros((8, 8, 4, 4), device=DEV), F32, 8, g)
+    assert tuple(wt.shape) == (4, 8, 4 * 8)
+    with pytest.raises(L.VtError, match="pass in_hw"):
+        ops.conv_dgrad(dy, wt, g, cin=8, cout=8)
+    with pytest.raises(L.VtError, match="are not the forward convolution's"):
+        ops.conv_dgrad(dy, wt, g, cin=8, cout=8, in_hw=(11, 8))
+    with pytest.raises(L.VtError, match="zero time pad"):
+        ops.conv_dgrad(dy, wt, g, cin=8, cout=8, in_hw=(8, 8), tmode=L.VT_TPAD_REPLICATE)
+    with pytest.raises(L.VtError, match="strides"):
+        ops.conv_dgrad(dy, wt, dataclasses.replace(g, sh=3), cin=8, cout=8, in_hw=(8, 8))
+    assert float(ops.conv_dgrad(dy, wt, g, cin=8, cout=8, in_hw=(8, 8)).abs().max()) == 0
     g1 = ops.ConvGeom(kh=4, kw=4, ph=1, pw=1, ph_hi=1, pw_hi=1)
-    with pytest.raises(L.VtError, match="vt_conv_dgrad serves stride 1"):
-        ops.conv_dgrad_strided(torch.zeros((1, 1, 7, 7, 8), device=DEV), wt, g1, cin=8, cout=8, in_hw=(8, 8))
+    dy1, wt1 = torch.zeros((1, 1, 7, 7, 8), device=DEV), ops.pack_conv_weight_dgrad(torch.zeros((8, 8, 4, 4), device=DEV), F32, 8)
+    assert tuple(wt1.shape) == (8, 16 * 8) and tuple(ops.conv_dgrad(dy1, wt1, g1, cin=8, cout=8, in_hw=(8, 8)).shape) == (1, 1, 8, 8, 8)
+    with pytest.raises(AssertionError):
+        ops.conv_dgrad(dy1, wt1, g1, cin=8, cout=8, in_hw=(9, 8))
 
 
 # ---- 5. arena: every new entry point reads and writes only inside its operands --------------------------------------------------------------
@@ -268,11 +281,53 @@ def test_arena_conv_dgrad_strided(with_acc, dtype):
     w = (torch.randn((cout, cin, 4, 4), generator=_gen(1)) * 0.2).to(DEV)
     dy = torch.randn((B, T, Ho, Wo, 24), generator=_gen(2)).to(dtype).to(DEV)
     acc = torch.randn((B, T, H, W, 16), generator=_gen(3)).to(dtype).to(DEV) if with_acc else None
-    ar = _direct(["vt_pack_conv_weight_dgrad_strided"], lambda: ops.pack_conv_weight_dgrad_strided(w, dtype, g, 24), lambda p: [_in("w", w), _out("out", p)])
+    ar = _direct(["vt_pack_conv_weight_dgrad"], lambda: ops.pack_conv_weight_dgrad(w, dtype, 24, g), lambda p: [_in("w", w), _out("out", p)])
     wt = ar.view("out", dtype, (4, cin, 4 * 24)).clone()
-    ar = _direct(["vt_conv_dgrad_strided"], lambda: ops.conv_dgrad_strided(dy, wt, g, cin=cin, cout=cout, in_hw=(H, W), acc=acc),
+    ar = _direct(["vt_conv_dgrad"], lambda: ops.conv_dgrad(dy, wt, g, cin=cin, cout=cout, in_hw=(H, W), acc=acc),
                  lambda dx: [_in("dy", dy), _in("wt", wt), _out("dx", dx, ld=16, c=cin)] + ([_in("acc", acc)] if with_acc else []))
     assert float(ar.view("dx", dtype, (B, T, H, W, 16))[..., cin:].float().abs().max()) == 0
+
+
+def _class_rows(w5, g, cout_p):
+    """the blocks [sh * sw, cin, ldw] of vt_pack_conv_weight_dgrad from the host class table: per class its taps in the table's (flipped)
+    order, the time taps flipped, Cin / Cout transposed, zeros in the pad channels and past the class's taps"""
+    from vidtok_amd.packing import strided_dgrad_classes
+
+    cout, cin, kt = w5.shape[:3]
+    ldw = kt * -(-g.kh // g.sh) * -(-g.kw // g.sw) * cout_p
+    blocks = []
+    for ch, cw in strided_dgrad_classes(g.kh, g.kw, g.sh, g.sw, g.ph, g.pw):
+        sub = w5.flip(2)[:, :, :, ch["taps"]][:, :, :, :, cw["taps"]].permute(1, 2, 3, 4, 0)          # [cin, kt, nkh, nkw, cout]
+        rows = F.pad(sub, (0, cout_p - cout)).reshape(cin, -1)
+        blocks.append(F.pad(rows, (0, ldw - rows.shape[1])))
+    return torch.stack(blocks)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_pack_conv_weight_dgrad_bits(dtype):
+    """the one packer against the host statements, bit for bit: at stride 1 with and without a geometry (pack_rows of
+    tests/test_decoder_backward_host.py, inside an arena), under a stride the blocks of the class table"""
+    from test_decoder_backward_host import pack_rows
+
+    ops, _ = _mods()
+    for shape, cs in (((20, 12, 3, 3, 3), 24), ((20, 12, 1, 4, 4), None)):
+        w = torch.randn(shape, generator=_gen(60))
+        wd = w.to(DEV)
+        kt, kh, kw = shape[2:]
+        want = pack_rows(w, cs or ops.pad_channels(20)).to(dtype)
+        ar = _direct(["vt_pack_conv_weight_dgrad"], lambda: ops.pack_conv_weight_dgrad(wd, dtype, cs), lambda p: [_in("w", wd), _out("out", p)])
+        plain = ar.view("out", dtype, tuple(want.shape)).cpu()
+        assert torch.equal(plain, want) and torch.equal(ops.pack_conv_weight_dgrad(wd, dtype, cs).cpu(), want)
+        g1 = ops.ConvGeom(kt=kt, kh=kh, kw=kw, pt=kt - 1, ph=1, pw=1, ph_hi=1, pw_hi=1)
+        with_geom = ops.pack_conv_weight_dgrad(wd, dtype, cs, g1)
+        assert tuple(with_geom.shape) == (1,) + tuple(want.shape) and torch.equal(with_geom[0].cpu(), want)
+        assert torch.equal(_class_rows(w, g1, cs or 24).to(dtype), want.unsqueeze(0))                    # the class table says the same
+    for gname, shape in (("k4 s2 p1", (20, 12, 1, 4, 4)), ("1x3x3 s21", (20, 12, 1, 3, 3))):
+        g = _strided_geoms()[gname]
+        w = torch.randn(shape, generator=_gen(61))
+        got = ops.pack_conv_weight_dgrad(w.to(DEV), dtype, 24, g)
+        want = _class_rows(w, g, 24).to(dtype)
+        assert tuple(got.shape) == tuple(want.shape) == (g.sh * g.sw, 12, want.shape[2]) and torch.equal(got.cpu(), want), gname
 
 
 def test_new_kernels_graph_capture_replays_bit_equal():
@@ -283,13 +338,13 @@ def test_new_kernels_graph_capture_replays_bit_equal():
     c = torch.randn((2, 1, 4, 6, 24), generator=_gen(40)).to(BF16).to(DEV)
     dy = torch.randn(c.shape, generator=_gen(41)).to(DEV)
     gamma, beta = torch.rand(20, device=DEV) + 0.5, torch.randn(20, device=DEV)
-    wt = ops.pack_conv_weight_dgrad_strided(torch.randn((20, 12, 4, 4), generator=_gen(42)).to(DEV), BF16, g, 24)
+    wt = ops.pack_conv_weight_dgrad(torch.randn((20, 12, 4, 4), generator=_gen(42)).to(DEV), BF16, 24, g)
 
     def run():
         mean, var, rstd = ops.batchnorm_stats(c, c=20)
         y = ops.batchnorm_act(c, mean, rstd, gamma, beta, SLOPE, c=20)
         dc, dg, db = ops.batchnorm_act_backward(c, dy, mean, rstd, gamma, beta, SLOPE, batch=True, c=20)
-        dx = ops.conv_dgrad_strided(dc, wt, g, cin=12, cout=20, in_hw=(9, 12))
+        dx = ops.conv_dgrad(dc, wt, g, cin=12, cout=20, in_hw=(9, 12))
         return [y, ops.leaky_relu_backward(dy, y, SLOPE), mean, var, dc, dg, db, dx]
 
     run()

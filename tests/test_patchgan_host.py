@@ -1,5 +1,5 @@
 """PatchGAN discriminator, everything that needs no GPU: the restatement against the reference class and against the recorded golden,
-the parity-class table of the strided data gradient, refusals, state_dict / checkpoint loading, repacking, the C-ABI surface."""
+the parity-class table of the data gradient and the domain of vt_conv_dgrad, refusals, state_dict / checkpoint loading, repacking, the C-ABI surface."""
 import json
 import os
 import re
@@ -16,8 +16,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", R.GOLDEN)
 # n ~ 1e4 terms a sum, through five layers and three normalisations; 1e-9 is far above that and far below any real difference
 TOL = 1e-9
 NEW_SYMBOLS = ("vt_batchnorm_stats_work_bytes", "vt_batchnorm_stats", "vt_batchnorm_act", "vt_batchnorm_act_backward_work_bytes",
-               "vt_batchnorm_act_backward", "vt_leaky_relu_backward", "vt_pack_conv_weight_dgrad_strided", "vt_conv_dgrad_strided_work_bytes",
-               "vt_conv_dgrad_strided")
+               "vt_batchnorm_act_backward", "vt_leaky_relu_backward")
 
 
 def _cases():
@@ -109,6 +108,21 @@ def test_strided_dgrad_classes(geom):
     assert torch.equal(dx, x.grad), float((dx - x.grad).abs().max())
 
 
+@pytest.mark.parametrize("k", [(3, 3, 1, 1), (4, 4, 1, 1), (1, 3, 0, 1)], ids=["k3 p1", "k4 p1", "1x3 p01"])
+def test_stride_one_is_one_class_with_mirrored_pads(k):
+    """at stride 1 the class table is the table dgrad_by_forward_conv (tests/test_decoder_backward_host.py) assumes: one class, every tap
+    flipped, front pad K - 1 - p, every pixel"""
+    from vidtok_amd.packing import strided_dgrad_classes
+
+    kh, kw, ph, pw = k
+    H, W = 5, 7
+    classes = strided_dgrad_classes(kh, kw, 1, 1, ph, pw, H, W)
+    assert len(classes) == 1
+    ch, cw = classes[0]
+    assert ch["taps"] == list(range(kh))[::-1] and cw["taps"] == list(range(kw))[::-1]
+    assert (ch["pad"], cw["pad"]) == (kh - 1 - ph, kw - 1 - pw) and (ch["n"], cw["n"]) == (H, W) and (ch["r"], cw["r"]) == (0, 0)
+
+
 # ---- (d) refusals ----------------------------------------------------------------------------------------------------------------
 def test_refusals():
     from vidtok_amd import lib as L
@@ -174,25 +188,55 @@ def test_symbols_declared_and_bound(built_lib):
         assert name in L.SIGNATURES and getattr(built_lib, name) is not None
 
 
-def test_dgrad_still_refuses_strides_and_strided_checks(built_lib):
+def test_conv_dgrad_domain(built_lib):
+    """vt_conv_dgrad serves st = 1 with sh, sw in {1, 2}; a stride takes a zero time pad, no ups, at most 4 taps an axis and class pads
+    that are not negative.  Host side: vt_conv_dgrad_work_bytes is the byte count, or -1 with a message"""
     import ctypes as C
 
     from vidtok_amd import lib as L
+    from vidtok_amd.packing import strided_axis_class
 
-    d = L.DgradDesc()
-    d.B, d.Ti, d.Hi, d.Wi, d.lddx, d.Cin = 2, 1, 9, 12, 16, 12
-    d.To, d.Ho, d.Wo, d.lddy, d.Cout = 1, 4, 6, 24, 20
-    d.KT, d.KH, d.KW, d.st, d.sh, d.sw = 1, 4, 4, 1, 2, 2
-    d.ph = d.pw = d.ph_hi = d.pw_hi = 1
-    d.dtype = d.dx_dtype = L.VT_F32
-    d.ldw = 4 * 24
-    assert built_lib.vt_conv_dgrad_work_bytes(C.byref(d)) == -1
-    assert "only stride-1 convolutions have a data gradient here" in built_lib.vt_last_error().decode()
+    def desc(**kw):
+        d = L.DgradDesc()
+        d.B, d.Ti, d.Hi, d.Wi, d.lddx, d.Cin = 2, 1, 9, 12, 16, 12
+        d.To, d.Ho, d.Wo, d.lddy, d.Cout = 1, 4, 6, 24, 20
+        d.KT, d.KH, d.KW, d.st, d.sh, d.sw = 1, 4, 4, 1, 2, 2
+        d.ph = d.pw = d.ph_hi = d.pw_hi = 1
+        d.dtype = d.dx_dtype = L.VT_F32
+        d.ldw = 4 * 24
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def refused(d, word):
+        assert built_lib.vt_conv_dgrad_work_bytes(C.byref(d)) == -1
+        msg = built_lib.vt_last_error().decode()
+        assert msg.startswith("vt_conv_dgrad:") and word in msg, msg
+
     # four classes of 5 x 6, 5 x 6, 4 x 6, 4 x 6 pixels, fp32 rows of lddx, each rounded up to 256 bytes
     want = sum((2 * nh * nw * 16 * 4 + 255) // 256 * 256 for nh in (5, 4) for nw in (6, 6))
-    assert built_lib.vt_conv_dgrad_strided_work_bytes(C.byref(d)) == want
-    d.Ho = 5                                                 # not the forward's extent
-    assert built_lib.vt_conv_dgrad_strided_work_bytes(C.byref(d)) == -1
-    d.Ho, d.sh, d.sw = 4, 1, 1                               # stride 1 belongs to vt_conv_dgrad
-    assert built_lib.vt_conv_dgrad_strided_work_bytes(C.byref(d)) == -1
-    assert "vt_conv_dgrad serves stride 1" in built_lib.vt_last_error().decode()
+    assert built_lib.vt_conv_dgrad_work_bytes(C.byref(desc())) == want
+    refused(desc(Ho=5), "extents")                                        # not the forward's extent
+    refused(desc(st=2, To=1), "strides")
+    refused(desc(sh=3, Ho=3), "strides")
+    refused(desc(ups_s=1, Ho=9, Wo=12), "no folded up-sampling")          # the extents of the up-sampled 18 x 24 input
+    refused(desc(tmode=L.VT_TPAD_REPLICATE), "zero time pad")
+    refused(desc(tmode=L.VT_TPAD_CACHE), "tmode")
+    refused(desc(KH=5, ph=2, Ho=5, ldw=6 * 24), "1 .. 4 taps")            # (9 + 2 + 1 - 5) / 2 + 1 rows; three row taps a class at the most
+    refused(desc(ph=4), "smaller than its kernel extent")
+    # a negative class pad: KH = 2, sh = 2, ph = 1: row class 1 holds the one tap 0, and (r + p) / s = 1 > nk - 1 = 0
+    ch = strided_axis_class(2, 2, 1, 1, 9)
+    assert ch["pad"] == len(ch["taps"]) - 1 - (1 + 1) // 2 == -1
+    refused(desc(KH=2, ph=1, ph_hi=0, Ho=5, ldw=2 * 24), "in front of dy's first pixel")      # (9 + 1 + 0 - 2) / 2 + 1 rows
+    # K < s: the class no tap reaches has nk = 0, so its pad nk - 1 - (r + p) / s is negative as well: refused like the above
+    ch = strided_axis_class(1, 2, 0, 1, 9)
+    assert ch["taps"] == [] and ch["pad"] == -1
+    refused(desc(KH=1, ph=0, ph_hi=0, Ho=5, ldw=2 * 24), "in front of dy's first pixel")      # (9 - 1) / 2 + 1 rows
+    # a class without a pixel (extent <= r) takes no launch and no workspace: one row, so row class 1 is empty
+    d = desc(Hi=1, Ho=1, KH=2, ph=0, ph_hi=1, ldw=2 * 24)                                     # (1 + 0 + 1 - 2) / 2 + 1 = 1 row; taps {0}, {1}: pads 0, 0
+    assert built_lib.vt_conv_dgrad_work_bytes(C.byref(d)) == 2 * ((2 * 1 * 6 * 16 * 4 + 255) // 256 * 256)
+    # stride 1 on the same entry: plain fp32 geometries need no workspace, everything else one exact, unpadded fp32 copy
+    d = desc(sh=1, sw=1, Ho=8, Wo=11, ldw=16 * 24)
+    assert built_lib.vt_conv_dgrad_work_bytes(C.byref(d)) == 0
+    d.tmode, d.KT, d.pt, d.ldw = L.VT_TPAD_REPLICATE, 2, 1, 2 * 16 * 24
+    assert built_lib.vt_conv_dgrad_work_bytes(C.byref(d)) == 2 * (1 + 1) * 9 * 12 * 16 * 4

@@ -62,7 +62,7 @@ def _conv_backward(s: ConvSite, x, dy, grads, acc=None, need_dx=True):
             grads[s.conv.bias] = db
     if not need_dx:
         return None
-    return ops.conv_dgrad(dy, s.dgrad_rows(dy.dtype, dy.shape[-1]), s.geom, cin=s.cin, cout=s.cout, tmode=s.clip_tmode, acc=acc)
+    return s.dgrad(dy, acc=acc)
 
 
 def _norm(norm, x, silu, dt):

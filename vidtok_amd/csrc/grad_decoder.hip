@@ -1,10 +1,13 @@
 // Data-gradient path of the decoder backward (include/vidtok_amd.h, "differentiable decode").
 //
-// vt_conv_dgrad: the gradient of a stride-1 vt_conv with respect to its stored input.  The MACs run on the FORWARD implicit-GEMM
-// tiles: dx is itself a convolution of dy with the tap-flipped, Cin/Cout-transposed weight (vt_pack_conv_weight_dgrad) and mirrored
-// pads, so vt_conv does the work at forward rates.  What a plain convolution cannot express is finished by grad_fold_kernel: the
-// KT - 1 virtual front frames of a replicate time pad add into frame 0, and the 2 / 2 x 2 positions of a folded nearest x2
-// up-sampling add into their source pixel -- fp32 sums in a fixed order, rounded once.
+// vt_conv_dgrad: the gradient of a vt_conv (row / column stride 1 or 2) with respect to its stored input.  The MACs run on the FORWARD
+// implicit-GEMM tiles: an input pixel of parity class (h mod sh, w mod sw) receives only the taps with (r + p - k) mod s = 0, so each
+// class is a stride-1 convolution of dy with a tap-flipped, Cin/Cout-transposed sub-kernel (vt_pack_conv_weight_dgrad) under mirrored
+// pads, and vt_conv does the work at forward rates; stride 1 is the one class that holds every tap.  What a plain convolution cannot
+// express is finished by one more launch.  One class (grad_fold_kernel): the KT - 1 virtual front frames of a replicate time pad add
+// into frame 0, and the 2 / 2 x 2 positions of a folded nearest x2 up-sampling add into their source pixel -- fp32 sums in a fixed
+// order, rounded once.  Several classes (strided_finish_kernel): they interleave, acc is added, one rounding.  The two stay apart
+// because one body for both was measurably slower on either side.
 //
 // The rest are the small kernels a decoder backward needs around the convolutions and LayerNorms: softmax backward, a batched
 // transpose (the attention GEMMs want K-contiguous operands), the alpha-mix of the time up-samplers forward and backward (with the
@@ -22,19 +25,43 @@ inline unsigned grid_for(long long n, int per_block = kBlock, long long cap = 16
   return (unsigned)std::max<long long>(1, std::min<long long>((n + per_block - 1) / per_block, cap));
 }
 
-// ---- transposed, tap-flipped weight pack ------------------------------------------------------------------------------------
-// out[ci][k], k = ((a' KH + p') KW + q') cout_p + co  <-  w[co][ci][KT-1-a'][KH-1-p'][KW-1-q'];  co >= Cout and k past the taps: 0
+// ---- parity classes of the input, per axis -----------------------------------------------------------------------------------
+// input positions i = s j + r receive only the taps k0, k0 + s, ... (nk of them): as a stride-1 convolution over dy that is the flipped
+// tap list under the front pad `pad`, n outputs.  s = 1: the one class r = 0 holds every tap under the mirrored pad K - 1 - p
+struct AxisClass {
+  int k0, nk, pad, n;
+};
+inline AxisClass axis_class(int K, int s, int p, int r, int extent) {
+  AxisClass a;
+  a.k0 = (r + p) % s;
+  a.nk = K > a.k0 ? (K - a.k0 + s - 1) / s : 0;
+  a.pad = a.nk - 1 - (r + p) / s;
+  a.n = extent > r ? (extent - r + s - 1) / s : 0;
+  return a;
+}
+
+// ---- transposed, tap-flipped weight pack, one block [Cin][ldw] per class ---------------------------------------------------------
+// out[cls][ci][k], k = ((a' nkh + p') nkw + q') cout_p + co  <-  w[co][ci][KT-1-a'][kh0 + sh (nkh-1-p')][kw0 + sw (nkw-1-q')]; the rest zero
 template <typename TO>
-__global__ __launch_bounds__(kBlock) void pack_dgrad_kernel(const float* __restrict__ w, TO* __restrict__ out, int Cout, int Cin, int cout_p,
-                                                            int KT, int KH, int KW, long long ldw) {
-  const int taps = KT * KH * KW;
-  const long long n = (long long)Cin * ldw;
+__global__ __launch_bounds__(kBlock) void pack_dgrad_kernel(const float* __restrict__ w, TO* __restrict__ out, int Cout, int Cin, int cout_p, int KT, int KH,
+                                                            int KW, int sh, int sw, int ph, int pw, long long ldw) {
+  const long long per = (long long)Cin * ldw;
+  const long long n = per * sh * sw;
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-    const long long ci = i / ldw;
-    const int k = (int)(i - ci * ldw);
-    const int j = k / cout_p, co = k - j * cout_p;
+    const int cls = (int)(i / per);
+    const long long j = i - cls * per;
+    const long long ci = j / ldw;
+    const int k = (int)(j - ci * ldw);
+    const int rh = cls / sw, rw = cls - rh * sw;
+    const int kh0 = (rh + ph) % sh, kw0 = (rw + pw) % sw;
+    const int nkh = KH > kh0 ? (KH - kh0 + sh - 1) / sh : 0, nkw = KW > kw0 ? (KW - kw0 + sw - 1) / sw : 0;
+    const int tap = k / cout_p, co = k - tap * cout_p;
     float v = 0.0f;
-    if (j < taps && co < Cout) v = w[((long long)co * Cin + ci) * taps + (taps - 1 - j)];     // flipping all three axes = reversing the row-major tap index
+    if (tap < KT * nkh * nkw && co < Cout) {
+      const int q = tap % nkw, pp = (tap / nkw) % nkh, a = tap / (nkw * nkh);
+      const int kt = KT - 1 - a, kh = kh0 + sh * (nkh - 1 - pp), kw = kw0 + sw * (nkw - 1 - q);
+      v = w[((((long long)co * Cin + ci) * KT + kt) * KH + kh) * KW + kw];
+    }
     out[i] = from_f32<TO>(v);
   }
 }
@@ -87,6 +114,51 @@ __global__ __launch_bounds__(kBlock) void grad_fold_kernel(const FoldArgs a) {
     TO* o = dx + ((((long long)b * a.T + t) * a.H + h) * a.W + w) * a.ldo + c0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = from_f32<TO>(c0 + e < a.C ? s[e] : 0.f);
+  }
+}
+
+// ---- the classes of a strided data gradient interleaved (+ acc), one rounding ----------------------------------------------------------
+struct FinishArgs {
+  const float* work;
+  const void* acc;
+  void* dx;
+  long long off[4];      // class (rh, rw) at off[rh * sw + rw] floats into work, or -1: no tap reaches the class (zeros)
+  int nh[4], nw[4];
+  int B, T, H, W, C, ld, lda, sh, sw;
+};
+
+template <typename TO>
+__global__ __launch_bounds__(kBlock) void strided_finish_kernel(const FinishArgs a) {
+  const TO* __restrict__ acc = static_cast<const TO*>(a.acc);
+  TO* __restrict__ dx = static_cast<TO*>(a.dx);
+  const int q = a.ld / 4;
+  const long long n = (long long)a.B * a.T * a.H * a.W * q;
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
+    const int c0 = (int)(i % q) * 4;
+    long long r = i / q;
+    const int w = (int)(r % a.W);
+    r /= a.W;
+    const int h = (int)(r % a.H);
+    const long long bt = r / a.H;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c0 < a.C) {
+      const int cls = (h % a.sh) * a.sw + (w % a.sw);
+      if (a.off[cls] >= 0) {
+        const float* p = a.work + a.off[cls] + ((bt * a.nh[cls] + h / a.sh) * a.nw[cls] + w / a.sw) * a.ld + c0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (c0 + e < a.C) s[e] = p[e];
+      }
+      if (acc) {
+        const TO* p = acc + ((bt * a.H + h) * a.W + w) * a.lda + c0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (c0 + e < a.C) s[e] += to_f32<TO>(p[e]);
+      }
+    }
+    TO* o = dx + ((bt * a.H + h) * a.W + w) * a.ld + c0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = from_f32<TO>(s[e]);
   }
 }
 
@@ -243,30 +315,87 @@ __global__ __launch_bounds__(kBlock) void grad_add_kernel(const T* __restrict__ 
 
 inline bool grad_dtype_ok(int dt) { return dt == VT_F32 || dt == VT_BF16; }
 
-// checks of a vt_dgrad_desc; fills the geometry of the convolution over dy.  rep = virtual front frames kept for the fold
-int dgrad_prepare(const vt_dgrad_desc* d, int* rep, bool* folded) {
+// what vt_conv_dgrad launches: the classes of the virtual (up-sampled) rows and columns and where each class convolution writes
+struct DgradPlan {
+  AxisClass ah[2], aw[2];
+  int64_t off[4];        // class rh * sw + rw at off[] bytes into work; -1: no tap or no pixel (zeros)
+  int64_t bytes;         // of work; 0: the one class is written into dx by its own launch
+  int rep;               // virtual front frames kept for the fold
+};
+
+// checks of a vt_dgrad_desc; fills the plan
+int dgrad_prepare(const vt_dgrad_desc* d, DgradPlan* p) {
   VT_CHECK_ARG(d != nullptr, "vt_conv_dgrad: null descriptor");
   VT_CHECK_ARG(grad_dtype_ok(d->dtype) && (d->dx_dtype == d->dtype || d->dx_dtype == VT_F32), "vt_conv_dgrad: dtype %d -> dx_dtype %d (fp32 or bf16 operands; dx in the operand type or fp32)",
                d->dtype, d->dx_dtype);
-  VT_CHECK_ARG(d->st == 1 && d->sh == 1 && d->sw == 1,
-               "vt_conv_dgrad: strides (%d, %d, %d): only stride-1 convolutions have a data gradient here (the decoder has no strided one)", d->st, d->sh, d->sw);
+  VT_CHECK_ARG(d->st == 1 && (d->sh == 1 || d->sh == 2) && (d->sw == 1 || d->sw == 2), "vt_conv_dgrad: strides (%d, %d, %d): st = 1 and sh, sw in {1, 2}", d->st, d->sh, d->sw);
+  const bool strided = d->sh + d->sw > 2;
   VT_CHECK_ARG(d->B > 0 && d->Ti > 0 && d->Hi > 0 && d->Wi > 0 && d->Cin > 0 && d->Cout > 0 && d->To > 0 && d->Ho > 0 && d->Wo > 0, "vt_conv_dgrad: bad dims");
   VT_CHECK_ARG(d->KT > 0 && d->KH > 0 && d->KW > 0 && d->KT * d->KH * d->KW <= 64, "vt_conv_dgrad: bad taps");
   VT_CHECK_ARG((d->ups_t | d->ups_s | 1) == 1, "vt_conv_dgrad: ups_t / ups_s are 0 or 1");
   VT_CHECK_ARG(d->tmode == VT_TPAD_ZERO || d->tmode == VT_TPAD_REPLICATE, "vt_conv_dgrad: tmode %d (zero or replicate: a whole clip, no chunk cache)", d->tmode);
+  VT_CHECK_ARG(!strided || (d->tmode == VT_TPAD_ZERO && d->ups_t == 0 && d->ups_s == 0 && d->KT <= 4 && d->KH <= 4 && d->KW <= 4),
+               "vt_conv_dgrad: strides (%d, %d) with tmode %d, ups (%d, %d), taps (%d, %d, %d): a strided geometry has a zero time pad, no folded up-sampling and 1 .. 4 taps an axis",
+               d->sh, d->sw, d->tmode, d->ups_t, d->ups_s, d->KT, d->KH, d->KW);
   VT_CHECK_ARG(d->pt >= 0 && d->pt < d->KT && d->pt_hi >= 0 && d->pt_hi < d->KT && d->ph >= 0 && d->ph < d->KH && d->ph_hi >= 0 && d->ph_hi < d->KH &&
                    d->pw >= 0 && d->pw < d->KW && d->pw_hi >= 0 && d->pw_hi < d->KW, "vt_conv_dgrad: a pad must be smaller than its kernel extent");
   const int Tv = d->Ti << d->ups_t, Hv = d->Hi << d->ups_s, Wv = d->Wi << d->ups_s;
-  VT_CHECK_ARG(d->To == Tv + d->pt + d->pt_hi - d->KT + 1 && d->Ho == Hv + d->ph + d->ph_hi - d->KH + 1 && d->Wo == Wv + d->pw + d->pw_hi - d->KW + 1,
+  VT_CHECK_ARG(d->To == Tv + d->pt + d->pt_hi - d->KT + 1 && Hv + d->ph + d->ph_hi >= d->KH && d->Ho == (Hv + d->ph + d->ph_hi - d->KH) / d->sh + 1 &&
+                   Wv + d->pw + d->pw_hi >= d->KW && d->Wo == (Wv + d->pw + d->pw_hi - d->KW) / d->sw + 1,
                "vt_conv_dgrad: dy extents (%d, %d, %d) are not the forward convolution's", d->To, d->Ho, d->Wo);
   const int vec = d->dtype == VT_BF16 ? 8 : 4;
   VT_CHECK_ARG(d->lddy >= d->Cout && d->lddy % vec == 0 && d->lddx >= d->Cin && d->lddx % 4 == 0, "vt_conv_dgrad: lddy %d / lddx %d", d->lddy, d->lddx);
-  VT_CHECK_ARG(d->ldw >= (int64_t)d->KT * d->KH * d->KW * d->lddy && d->ldw % vec == 0, "vt_conv_dgrad: ldw %d (taps x lddy of vt_pack_conv_weight_dgrad)", d->ldw);
+  const int nkh = (d->KH + d->sh - 1) / d->sh, nkw = (d->KW + d->sw - 1) / d->sw;
+  VT_CHECK_ARG(d->ldw >= (int64_t)d->KT * nkh * nkw * d->lddy && d->ldw % vec == 0, "vt_conv_dgrad: ldw %d (vt_pack_conv_weight_dgrad: KT ceil(KH/sh) ceil(KW/sw) lddy)", d->ldw);
   VT_CHECK_ARG(d->acc == nullptr || d->ldacc >= d->Cin, "vt_conv_dgrad: ldacc %d", d->ldacc);
-  *rep = (d->tmode == VT_TPAD_REPLICATE) ? d->pt : 0;
-  // straight from the convolution's epilogue only where that is the single rounding: fp32 results of a plain geometry
-  *folded = *rep > 0 || d->ups_t || d->ups_s || d->dx_dtype != VT_F32;
+  p->rep = (d->tmode == VT_TPAD_REPLICATE) ? d->pt : 0;
+  // straight from the convolution's epilogue only where that is the single rounding: fp32 results of a plain stride-1 geometry
+  const bool folded = strided || p->rep > 0 || d->ups_t || d->ups_s || d->dx_dtype != VT_F32;
+  int64_t at = 0;
+  for (int rh = 0; rh < d->sh; ++rh) p->ah[rh] = axis_class(d->KH, d->sh, d->ph, rh, Hv);
+  for (int rw = 0; rw < d->sw; ++rw) p->aw[rw] = axis_class(d->KW, d->sw, d->pw, rw, Wv);
+  for (int rh = 0; rh < d->sh; ++rh)
+    for (int rw = 0; rw < d->sw; ++rw) {
+      const AxisClass &h = p->ah[rh], &w = p->aw[rw];
+      VT_CHECK_ARG(h.pad >= 0 && w.pad >= 0, "vt_conv_dgrad: pads (%d, %d) put a class convolution in front of dy's first pixel", d->ph, d->pw);
+      const bool empty = h.nk == 0 || w.nk == 0 || h.n == 0 || w.n == 0;
+      p->off[rh * d->sw + rw] = empty ? -1 : at;
+      // several classes start on 256-byte boundaries; a lone class takes exactly its size
+      const int64_t sz = (int64_t)d->B * (p->rep + Tv) * h.n * w.n * d->lddx * 4;
+      if (folded && !empty) at += strided ? (sz + 255) / 256 * 256 : sz;
+    }
+  p->bytes = at;
   return VT_OK;
+}
+
+// the stride-1 convolution over dy that computes class (rh, rw): flipped sub-kernel, mirrored pads, fp32 out
+vt_conv_desc class_conv(const vt_dgrad_desc* d, const DgradPlan& p, int rh, int rw) {
+  const AxisClass &h = p.ah[rh], &w = p.aw[rw];
+  const int cls = rh * d->sw + rw;
+  vt_conv_desc c;
+  memset(&c, 0, sizeof(c));
+  c.x = d->dy;
+  c.w = static_cast<const char*>(d->wt) + (int64_t)cls * d->Cin * d->ldw * (d->dtype == VT_BF16 ? 2 : 4);
+  c.B = d->B; c.Ti = d->To; c.Hi = d->Ho; c.Wi = d->Wo; c.Cin = d->lddy;
+  c.To = p.rep + (d->Ti << d->ups_t); c.Ho = h.n; c.Wo = w.n; c.Cout = d->Cin;
+  c.ldw = d->ldw; c.ldy = d->lddx;
+  c.KT = d->KT; c.KH = h.nk; c.KW = w.nk;
+  c.st = c.sh = c.sw = 1;
+  // mirrored pads: virtual-input position i receives dy[i - (K-1) + a'] through flipped tap a'; the output starts at the first REAL
+  // position (zero pad: i = pt) or at the first virtual one (replicate: i = 0, the front frames are folded afterwards)
+  c.pt = p.rep > 0 ? d->KT - 1 : d->KT - 1 - d->pt;
+  c.ph = h.pad; c.pw = w.pad;
+  c.tmode = VT_TPAD_ZERO;
+  c.out_layout = VT_NDHWC;
+  c.dtype = d->dtype; c.out_dtype = VT_F32;
+  c.nbatch = 1;
+  if (p.bytes > 0) {
+    c.y = static_cast<char*>(d->work) + p.off[cls];
+  } else {
+    c.y = d->dx;
+    if (d->acc) { c.res_mode = VT_RES_ADD; c.res = d->acc; c.Tr = d->Ti; c.ldr = d->ldacc; }
+  }
+  return c;
 }
 
 }  // namespace
@@ -274,26 +403,26 @@ int dgrad_prepare(const vt_dgrad_desc* d, int* rep, bool* folded) {
 extern "C" int vt_dgrad_desc_size(void) { return (int)sizeof(vt_dgrad_desc); }
 
 extern "C" int vt_pack_conv_weight_dgrad(const float* w, void* out, int32_t out_dtype, int32_t Cout, int32_t Cin, int32_t cout_p, int32_t KT, int32_t KH,
-                                         int32_t KW, int64_t ldw, vt_stream stream_) {
+                                         int32_t KW, int32_t sh, int32_t sw, int32_t ph, int32_t pw, int64_t ldw, vt_stream stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(w && out && Cout > 0 && Cin > 0 && cout_p >= Cout && KT > 0 && KH > 0 && KW > 0, "vt_pack_conv_weight_dgrad: bad arguments");
   VT_CHECK_ARG(grad_dtype_ok(out_dtype), "vt_pack_conv_weight_dgrad: out_dtype %d (fp32 or bf16)", out_dtype);
-  VT_CHECK_ARG(ldw >= (int64_t)KT * KH * KW * cout_p, "vt_pack_conv_weight_dgrad: ldw %lld", (long long)ldw);
-  const unsigned grid = grid_for((long long)Cin * ldw, kBlock, 8192);
+  VT_CHECK_ARG((sh == 1 || sh == 2) && (sw == 1 || sw == 2) && ph >= 0 && ph < KH && pw >= 0 && pw < KW, "vt_pack_conv_weight_dgrad: strides (%d, %d) in {1, 2}, pads (%d, %d) below the taps",
+               sh, sw, ph, pw);
+  VT_CHECK_ARG(sh + sw == 2 || (KT <= 4 && KH <= 4 && KW <= 4), "vt_pack_conv_weight_dgrad: taps (%d, %d, %d): 1 .. 4 an axis under a stride", KT, KH, KW);
+  VT_CHECK_ARG(ldw >= (int64_t)KT * ((KH + sh - 1) / sh) * ((KW + sw - 1) / sw) * cout_p, "vt_pack_conv_weight_dgrad: ldw %lld", (long long)ldw);
+  const unsigned grid = grid_for((long long)sh * sw * Cin * ldw, kBlock, 8192);
   if (out_dtype == VT_F32)
-    hipLaunchKernelGGL(pack_dgrad_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, w, static_cast<float*>(out), Cout, Cin, cout_p, KT, KH, KW, (long long)ldw);
+    hipLaunchKernelGGL(pack_dgrad_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, w, static_cast<float*>(out), Cout, Cin, cout_p, KT, KH, KW, sh, sw, ph, pw, (long long)ldw);
   else
-    hipLaunchKernelGGL(pack_dgrad_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, w, static_cast<bf16_t*>(out), Cout, Cin, cout_p, KT, KH, KW, (long long)ldw);
+    hipLaunchKernelGGL(pack_dgrad_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, w, static_cast<bf16_t*>(out), Cout, Cin, cout_p, KT, KH, KW, sh, sw, ph, pw, (long long)ldw);
   VT_CHECK_LAUNCH();
   return VT_OK;
 }
 
 extern "C" int64_t vt_conv_dgrad_work_bytes(const vt_dgrad_desc* d) {
-  int rep = 0;
-  bool folded = false;
-  if (dgrad_prepare(d, &rep, &folded) != VT_OK) return -1;
-  if (!folded) return 0;
-  return (int64_t)d->B * (rep + (d->Ti << d->ups_t)) * (d->Hi << d->ups_s) * (d->Wi << d->ups_s) * d->lddx * 4;
+  DgradPlan p;
+  return dgrad_prepare(d, &p) == VT_OK ? p.bytes : -1;
 }
 
 extern "C" int vt_grad_fold(const void* src, int32_t src_dtype, const void* acc, void* dx, int32_t dx_dtype, int32_t B, int32_t T, int32_t H, int32_t W, int32_t C, int32_t lds,
@@ -312,42 +441,41 @@ extern "C" int vt_grad_fold(const void* src, int32_t src_dtype, const void* acc,
   return VT_OK;
 }
 
-extern "C" int vt_conv_dgrad(const vt_dgrad_desc* d, vt_stream stream) {
-  int rep = 0;
-  bool folded = false;
-  const int rc = dgrad_prepare(d, &rep, &folded);
+extern "C" int vt_conv_dgrad(const vt_dgrad_desc* d, vt_stream stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  DgradPlan p;
+  const int rc = dgrad_prepare(d, &p);
   if (rc != VT_OK) return rc;
   VT_CHECK_ARG(d->dy && d->wt && d->dx, "vt_conv_dgrad: null tensor pointer");
-  const int Tv = d->Ti << d->ups_t, Hv = d->Hi << d->ups_s, Wv = d->Wi << d->ups_s;
-  vt_conv_desc c;
-  memset(&c, 0, sizeof(c));
-  c.x = d->dy; c.w = d->wt;
-  c.B = d->B; c.Ti = d->To; c.Hi = d->Ho; c.Wi = d->Wo; c.Cin = d->lddy;
-  c.To = rep + Tv; c.Ho = Hv; c.Wo = Wv; c.Cout = d->Cin;
-  c.ldw = d->ldw; c.ldy = d->lddx;
-  c.KT = d->KT; c.KH = d->KH; c.KW = d->KW;
-  c.st = c.sh = c.sw = 1;
-  // mirrored pads: virtual-input position i receives dy[i - (K-1) + a'] through flipped tap a'; the output starts at the first REAL
-  // position (zero pad: i = pt) or at the first virtual one (replicate: i = 0, the front frames are folded afterwards)
-  c.pt = rep > 0 ? d->KT - 1 : d->KT - 1 - d->pt;
-  c.ph = d->KH - 1 - d->ph; c.pw = d->KW - 1 - d->pw;
-  c.tmode = VT_TPAD_ZERO;
-  c.out_layout = VT_NDHWC;
-  c.dtype = d->dtype; c.out_dtype = VT_F32;
-  c.nbatch = 1;
-  if (!folded) {
-    c.y = d->dx;
-    if (d->acc) { c.res_mode = VT_RES_ADD; c.res = d->acc; c.Tr = d->Ti; c.ldr = d->ldacc; }
-    return vt_conv(&c, stream);
-  }
-  const int64_t need = (int64_t)d->B * (rep + Tv) * Hv * Wv * d->lddx * 4;
-  VT_CHECK_ARG(d->work != nullptr && d->work_bytes >= need && (reinterpret_cast<uintptr_t>(d->work) & 15) == 0, "vt_conv_dgrad: workspace of %lld bytes needed (vt_conv_dgrad_work_bytes)",
-               (long long)need);
-  c.y = d->work;
-  const int rc2 = vt_conv(&c, stream);
-  if (rc2 != VT_OK) return rc2;
-  return vt_grad_fold(d->work, VT_F32, d->acc, d->dx, d->dx_dtype, d->B, d->Ti, d->Hi, d->Wi, d->Cin, d->lddx, d->ldacc, d->lddx, rep, d->ups_t,
-                      d->ups_s, stream);
+  VT_CHECK_ARG(p.bytes == 0 || (d->work != nullptr && d->work_bytes >= p.bytes && (reinterpret_cast<uintptr_t>(d->work) & 15) == 0),
+               "vt_conv_dgrad: workspace of %lld bytes needed (vt_conv_dgrad_work_bytes)", (long long)p.bytes);
+  FinishArgs f;
+  memset(&f, 0, sizeof(f));
+  for (int rh = 0; rh < d->sh; ++rh)
+    for (int rw = 0; rw < d->sw; ++rw) {
+      const int cls = rh * d->sw + rw;
+      f.off[cls] = p.off[cls] < 0 ? -1 : p.off[cls] / 4;
+      f.nh[cls] = p.ah[rh].n;
+      f.nw[cls] = p.aw[rw].n;
+      if (p.off[cls] < 0) continue;
+      const vt_conv_desc c = class_conv(d, p, rh, rw);
+      const int rc2 = vt_conv(&c, stream_);
+      if (rc2 != VT_OK) return rc2;
+    }
+  if (p.bytes == 0) return VT_OK;                     // the one class went straight into dx
+  if (d->sh + d->sw == 2)                             // one class: replicate front frames, folded up-sampling, acc, one rounding
+    return vt_grad_fold(d->work, VT_F32, d->acc, d->dx, d->dx_dtype, d->B, d->Ti, d->Hi, d->Wi, d->Cin, d->lddx, d->ldacc, d->lddx, p.rep, d->ups_t, d->ups_s, stream_);
+  f.work = static_cast<const float*>(d->work);
+  f.acc = d->acc;
+  f.dx = d->dx;
+  f.B = d->B; f.T = d->Ti; f.H = d->Hi; f.W = d->Wi; f.C = d->Cin; f.ld = d->lddx; f.lda = d->ldacc; f.sh = d->sh; f.sw = d->sw;
+  const unsigned grid = grid_for((long long)d->B * d->Ti * d->Hi * d->Wi * (d->lddx / 4));
+  if (d->dx_dtype == VT_F32)
+    hipLaunchKernelGGL(strided_finish_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, f);
+  else
+    hipLaunchKernelGGL(strided_finish_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, f);
+  VT_CHECK_LAUNCH();
+  return VT_OK;
 }
 
 extern "C" int vt_softmax_rows_backward(const void* p, int64_t ldp, const float* dp, void* ds, int64_t ldo, int32_t dtype, int64_t rows, int32_t cols, float scale,

@@ -1,14 +1,9 @@
 // The kernels of the 2-D PatchGAN discriminator (include/vidtok_amd.h, "PatchGAN discriminator"): batch-statistics BatchNorm with
-// LeakyReLU forward and backward, the LeakyReLU backward of the un-normalised first layer, and the data gradient of a convolution with
-// row / column stride 2.
+// LeakyReLU forward and backward, and the LeakyReLU backward of the un-normalised first layer.
 //
 // Rows are NDHWC pixels [M][ld]; a lane owns 8 consecutive channels of a row (row8.h), a workgroup walks a fixed range of rows.  Every
 // sum over rows is a per-workgroup partial in the caller's `work`, added in index order by a second launch (fp64 in that launch): no
 // atomics, two runs give the same bits, nothing allocates or synchronises.
-//
-// vt_conv_dgrad_strided: an input pixel of parity class (rh, rw) = (h mod sh, w mod sw) receives only the taps with (r + p - k) mod s = 0,
-// so each class is a stride-1 convolution of dy with a flipped, transposed sub-kernel (vt_pack_conv_weight_dgrad_strided).  The classes run
-// on vt_conv unchanged, fp32 into `work`; strided_finish_kernel interleaves them, adds acc and rounds once.  No zero-dilated dy.
 #include <algorithm>
 
 #include "row8.h"
@@ -258,135 +253,6 @@ __global__ __launch_bounds__(kBlock) void leaky_bwd_kernel(const TD* __restrict_
 
 inline unsigned grid_for(int64_t n, int64_t cap = 16384) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap)); }
 
-// ---- strided data gradient ---------------------------------------------------------------------------------------------------------------
-// one axis of a parity class r: the taps k0, k0 + s, ... (nk of them), the front pad of the class convolution over dy, its output extent
-struct AxisClass {
-  int k0, nk, pad, n;
-};
-inline AxisClass axis_class(int K, int s, int p, int r, int extent) {
-  AxisClass a;
-  a.k0 = (r + p) % s;
-  a.nk = K > a.k0 ? (K - a.k0 + s - 1) / s : 0;
-  a.pad = a.nk - 1 - (r + p) / s;
-  a.n = extent > r ? (extent - r + s - 1) / s : 0;
-  return a;
-}
-
-// out[cls][ci][k], k = ((a' nkh + p') nkw + q') cout_p + co  <-  w[co][ci][KT-1-a'][kh0 + sh (nkh-1-p')][kw0 + sw (nkw-1-q')]; the rest zero
-template <typename TO>
-__global__ __launch_bounds__(kBlock) void pack_dgrad_strided_kernel(const float* __restrict__ w, TO* __restrict__ out, int Cout, int Cin, int cout_p, int KT,
-                                                                    int KH, int KW, int sh, int sw, int ph, int pw, long long ldw) {
-  const long long per = (long long)Cin * ldw;
-  const long long n = per * sh * sw;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-    const int cls = (int)(i / per);
-    const long long j = i - cls * per;
-    const long long ci = j / ldw;
-    const int k = (int)(j - ci * ldw);
-    const int rh = cls / sw, rw = cls - rh * sw;
-    const int kh0 = (rh + ph) % sh, kw0 = (rw + pw) % sw;
-    const int nkh = KH > kh0 ? (KH - kh0 + sh - 1) / sh : 0, nkw = KW > kw0 ? (KW - kw0 + sw - 1) / sw : 0;
-    const int tap = k / cout_p, co = k - tap * cout_p;
-    float v = 0.0f;
-    if (tap < KT * nkh * nkw && co < Cout) {
-      const int q = tap % nkw, pp = (tap / nkw) % nkh, a = tap / (nkw * nkh);
-      const int kt = KT - 1 - a, kh = kh0 + sh * (nkh - 1 - pp), kw = kw0 + sw * (nkw - 1 - q);
-      v = w[((((long long)co * Cin + ci) * KT + kt) * KH + kh) * KW + kw];
-    }
-    out[i] = from_f32<TO>(v);
-  }
-}
-
-struct FinishArgs {
-  const float* work;
-  const void* acc;
-  void* dx;
-  long long off[4];      // class (rh, rw) at off[rh * sw + rw] floats into work, or -1: no tap reaches the class (zeros)
-  int nh[4], nw[4];
-  int B, T, H, W, C, ld, lda, sh, sw;
-};
-
-template <typename TO>
-__global__ __launch_bounds__(kBlock) void strided_finish_kernel(const FinishArgs a) {
-  const TO* __restrict__ acc = static_cast<const TO*>(a.acc);
-  TO* __restrict__ dx = static_cast<TO*>(a.dx);
-  const int q = a.ld / 4;
-  const long long n = (long long)a.B * a.T * a.H * a.W * q;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
-    const int c0 = (int)(i % q) * 4;
-    long long r = i / q;
-    const int w = (int)(r % a.W);
-    r /= a.W;
-    const int h = (int)(r % a.H);
-    const long long bt = r / a.H;
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    if (c0 < a.C) {
-      const int cls = (h % a.sh) * a.sw + (w % a.sw);
-      if (a.off[cls] >= 0) {
-        const float* p = a.work + a.off[cls] + ((bt * a.nh[cls] + h / a.sh) * a.nw[cls] + w / a.sw) * a.ld + c0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (c0 + e < a.C) s[e] = p[e];
-      }
-      if (acc) {
-        const TO* p = acc + ((bt * a.H + h) * a.W + w) * a.lda + c0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (c0 + e < a.C) s[e] += to_f32<TO>(p[e]);
-      }
-    }
-    TO* o = dx + ((bt * a.H + h) * a.W + w) * a.ld + c0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = from_f32<TO>(s[e]);
-  }
-}
-
-struct StridedPlan {
-  AxisClass ah[2], aw[2];
-  int64_t off[4];        // bytes into work
-  int64_t bytes;
-};
-
-int strided_prepare(const vt_dgrad_desc* d, StridedPlan* p) {
-  VT_CHECK_ARG(d != nullptr, "vt_conv_dgrad_strided: null descriptor");
-  VT_CHECK_ARG(pg_dtype_ok(d->dtype) && (d->dx_dtype == d->dtype || d->dx_dtype == VT_F32),
-               "vt_conv_dgrad_strided: dtype %d -> dx_dtype %d (fp32 or bf16 operands; dx in the operand type or fp32)", d->dtype, d->dx_dtype);
-  VT_CHECK_ARG(d->st == 1 && (d->sh == 1 || d->sh == 2) && (d->sw == 1 || d->sw == 2) && d->sh + d->sw > 2,
-               "vt_conv_dgrad_strided: strides (%d, %d, %d): st = 1 and sh, sw in {1, 2} with at least one 2 (vt_conv_dgrad serves stride 1)", d->st, d->sh, d->sw);
-  VT_CHECK_ARG(d->tmode == VT_TPAD_ZERO && d->ups_t == 0 && d->ups_s == 0, "vt_conv_dgrad_strided: tmode %d, ups (%d, %d): zero time pad, no folded up-sampling",
-               d->tmode, d->ups_t, d->ups_s);
-  VT_CHECK_ARG(d->B > 0 && d->Ti > 0 && d->Hi > 0 && d->Wi > 0 && d->Cin > 0 && d->Cout > 0 && d->To > 0 && d->Ho > 0 && d->Wo > 0, "vt_conv_dgrad_strided: bad dims");
-  VT_CHECK_ARG(d->KT > 0 && d->KT <= 4 && d->KH > 0 && d->KH <= 4 && d->KW > 0 && d->KW <= 4, "vt_conv_dgrad_strided: taps (%d, %d, %d): 1 .. 4 an axis", d->KT, d->KH, d->KW);
-  VT_CHECK_ARG(d->pt >= 0 && d->pt < d->KT && d->pt_hi >= 0 && d->pt_hi < d->KT && d->ph >= 0 && d->ph < d->KH && d->ph_hi >= 0 && d->ph_hi < d->KH && d->pw >= 0 &&
-                   d->pw < d->KW && d->pw_hi >= 0 && d->pw_hi < d->KW, "vt_conv_dgrad_strided: a pad must be smaller than its kernel extent");
-  VT_CHECK_ARG(d->To == d->Ti + d->pt + d->pt_hi - d->KT + 1 && d->Ho == (d->Hi + d->ph + d->ph_hi - d->KH) / d->sh + 1 && d->Hi + d->ph + d->ph_hi >= d->KH &&
-                   d->Wo == (d->Wi + d->pw + d->pw_hi - d->KW) / d->sw + 1 && d->Wi + d->pw + d->pw_hi >= d->KW,
-               "vt_conv_dgrad_strided: dy extents (%d, %d, %d) are not the forward convolution's", d->To, d->Ho, d->Wo);
-  const int vec = d->dtype == VT_BF16 ? 8 : 4;
-  VT_CHECK_ARG(d->lddy >= d->Cout && d->lddy % vec == 0 && d->lddx >= d->Cin && d->lddx % 4 == 0, "vt_conv_dgrad_strided: lddy %d / lddx %d", d->lddy, d->lddx);
-  const int nkh = (d->KH + d->sh - 1) / d->sh, nkw = (d->KW + d->sw - 1) / d->sw;
-  VT_CHECK_ARG(d->ldw >= (int64_t)d->KT * nkh * nkw * d->lddy && d->ldw % vec == 0, "vt_conv_dgrad_strided: ldw %d (vt_pack_conv_weight_dgrad_strided: KT ceil(KH/sh) ceil(KW/sw) lddy)",
-               d->ldw);
-  VT_CHECK_ARG(d->acc == nullptr || d->ldacc >= d->Cin, "vt_conv_dgrad_strided: ldacc %d", d->ldacc);
-  int64_t at = 0;
-  for (int rh = 0; rh < d->sh; ++rh) p->ah[rh] = axis_class(d->KH, d->sh, d->ph, rh, d->Hi);
-  for (int rw = 0; rw < d->sw; ++rw) p->aw[rw] = axis_class(d->KW, d->sw, d->pw, rw, d->Wi);
-  for (int rh = 0; rh < d->sh; ++rh)
-    for (int rw = 0; rw < d->sw; ++rw) {
-      const AxisClass &h = p->ah[rh], &w = p->aw[rw];
-      VT_CHECK_ARG(h.pad >= 0 && w.pad >= 0, "vt_conv_dgrad_strided: pads (%d, %d) put a class convolution in front of dy's first pixel", d->ph, d->pw);
-      const int cls = rh * d->sw + rw;
-      if (h.nk == 0 || w.nk == 0 || h.n == 0 || w.n == 0) {
-        p->off[cls] = -1;
-        continue;
-      }
-      p->off[cls] = at;
-      at += align256((int64_t)d->B * d->Ti * h.n * w.n * d->lddx * 4);
-    }
-  p->bytes = at;
-  return VT_OK;
-}
-
 }  // namespace
 
 extern "C" int64_t vt_batchnorm_stats_work_bytes(int64_t M, int32_t C) {
@@ -508,81 +374,6 @@ extern "C" int vt_leaky_relu_backward(const void* dy, int32_t dy_dtype, const vo
   else
     hipLaunchKernelGGL((leaky_bwd_kernel<bf16_t, bf16_t>), dim3(grid), dim3(kBlock), 0, stream, static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(y),
                        static_cast<bf16_t*>(dx), slope, n / 8);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
-}
-
-extern "C" int vt_pack_conv_weight_dgrad_strided(const float* w, void* out, int32_t out_dtype, int32_t Cout, int32_t Cin, int32_t cout_p, int32_t KT, int32_t KH,
-                                                 int32_t KW, int32_t sh, int32_t sw, int32_t ph, int32_t pw, int64_t ldw, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  VT_CHECK_ARG(w && out && Cout > 0 && Cin > 0 && cout_p >= Cout && KT > 0 && KH > 0 && KW > 0 && KT <= 4 && KH <= 4 && KW <= 4, "vt_pack_conv_weight_dgrad_strided: bad arguments");
-  VT_CHECK_ARG(pg_dtype_ok(out_dtype), "vt_pack_conv_weight_dgrad_strided: out_dtype %d (fp32 or bf16)", out_dtype);
-  VT_CHECK_ARG((sh == 1 || sh == 2) && (sw == 1 || sw == 2) && ph >= 0 && ph < KH && pw >= 0 && pw < KW, "vt_pack_conv_weight_dgrad_strided: strides (%d, %d) in {1, 2}, pads (%d, %d) below the taps",
-               sh, sw, ph, pw);
-  VT_CHECK_ARG(ldw >= (int64_t)KT * ((KH + sh - 1) / sh) * ((KW + sw - 1) / sw) * cout_p, "vt_pack_conv_weight_dgrad_strided: ldw %lld", (long long)ldw);
-  const unsigned grid = grid_for((int64_t)sh * sw * Cin * ldw, 8192);
-  if (out_dtype == VT_F32)
-    hipLaunchKernelGGL(pack_dgrad_strided_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, w, static_cast<float*>(out), Cout, Cin, cout_p, KT, KH, KW, sh, sw, ph, pw,
-                       (long long)ldw);
-  else
-    hipLaunchKernelGGL(pack_dgrad_strided_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, w, static_cast<bf16_t*>(out), Cout, Cin, cout_p, KT, KH, KW, sh, sw, ph, pw,
-                       (long long)ldw);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
-}
-
-extern "C" int64_t vt_conv_dgrad_strided_work_bytes(const vt_dgrad_desc* d) {
-  StridedPlan p;
-  if (strided_prepare(d, &p) != VT_OK) return -1;
-  return p.bytes;
-}
-
-extern "C" int vt_conv_dgrad_strided(const vt_dgrad_desc* d, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  StridedPlan p;
-  const int rc = strided_prepare(d, &p);
-  if (rc != VT_OK) return rc;
-  VT_CHECK_ARG(d->dy && d->wt && d->dx, "vt_conv_dgrad_strided: null tensor pointer");
-  VT_CHECK_ARG(p.bytes == 0 || (d->work != nullptr && d->work_bytes >= p.bytes && (reinterpret_cast<uintptr_t>(d->work) & 15) == 0),
-               "vt_conv_dgrad_strided: workspace of %lld bytes needed (vt_conv_dgrad_strided_work_bytes)", (long long)p.bytes);
-  const int es = d->dtype == VT_BF16 ? 2 : 4;
-  FinishArgs f;
-  memset(&f, 0, sizeof(f));
-  for (int rh = 0; rh < d->sh; ++rh)
-    for (int rw = 0; rw < d->sw; ++rw) {
-      const int cls = rh * d->sw + rw;
-      const AxisClass &h = p.ah[rh], &w = p.aw[rw];
-      f.off[cls] = p.off[cls] < 0 ? -1 : p.off[cls] / 4;
-      f.nh[cls] = h.n;
-      f.nw[cls] = w.n;
-      if (p.off[cls] < 0) continue;
-      vt_conv_desc c;
-      memset(&c, 0, sizeof(c));
-      c.x = d->dy;
-      c.w = static_cast<const char*>(d->wt) + (int64_t)cls * d->Cin * d->ldw * es;
-      c.y = static_cast<char*>(d->work) + p.off[cls];
-      c.B = d->B; c.Ti = d->To; c.Hi = d->Ho; c.Wi = d->Wo; c.Cin = d->lddy;
-      c.To = d->Ti; c.Ho = h.n; c.Wo = w.n; c.Cout = d->Cin;
-      c.ldw = d->ldw; c.ldy = d->lddx;
-      c.KT = d->KT; c.KH = h.nk; c.KW = w.nk;
-      c.st = c.sh = c.sw = 1;
-      c.pt = d->KT - 1 - d->pt; c.ph = h.pad; c.pw = w.pad;
-      c.tmode = VT_TPAD_ZERO;
-      c.out_layout = VT_NDHWC;
-      c.dtype = d->dtype; c.out_dtype = VT_F32;
-      c.nbatch = 1;
-      const int rc2 = vt_conv(&c, stream_);
-      if (rc2 != VT_OK) return rc2;
-    }
-  f.work = static_cast<const float*>(d->work);
-  f.acc = d->acc;
-  f.dx = d->dx;
-  f.B = d->B; f.T = d->Ti; f.H = d->Hi; f.W = d->Wi; f.C = d->Cin; f.ld = d->lddx; f.lda = d->ldacc; f.sh = d->sh; f.sw = d->sw;
-  const unsigned grid = grid_for((int64_t)d->B * d->Ti * d->Hi * d->Wi * (d->lddx / 4));
-  if (d->dx_dtype == VT_F32)
-    hipLaunchKernelGGL(strided_finish_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, f);
-  else
-    hipLaunchKernelGGL(strided_finish_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, f);
   VT_CHECK_LAUNCH();
   return VT_OK;
 }

@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from . import lib as L
 from . import ops
-from .packing import PackedCache
+from .packing import ConvSite
 
 SLOPE = 0.2
 _MODES = (torch.float32, torch.bfloat16)
@@ -40,10 +40,8 @@ class _Layer:
     def __init__(self, conv, norm, act):
         self.conv, self.norm, self.act = conv, norm, act
         s = conv.stride[0]
-        self.geom = ops.ConvGeom(kh=4, kw=4, sh=s, sw=s, ph=1, pw=1, ph_hi=1, pw_hi=1)
-        self.cin, self.cout = conv.in_channels, conv.out_channels
-        self.pack = PackedCache()
-        self.dgrad = {}              # dtype -> (validity key, rows): the data-gradient pack of this convolution
+        self.site = ConvSite(conv, ops.ConvGeom(kh=4, kw=4, sh=s, sw=s, ph=1, pw=1, ph_hi=1, pw_hi=1))
+        self.geom, self.cin, self.cout = self.site.geom, self.site.cin, self.site.cout
 
 
 class NLayerDiscriminator(nn.Module):
@@ -109,13 +107,7 @@ class NLayerDiscriminator(nn.Module):
         return self
 
     def _dtype_now(self, x):
-        dev = x.device.type
-        try:
-            on = torch.is_autocast_enabled(dev)
-            adt = torch.get_autocast_dtype(dev) if on else None
-        except (TypeError, AttributeError, RuntimeError):
-            on = torch.is_autocast_enabled()
-            adt = torch.get_autocast_gpu_dtype() if on else None
+        on, adt = ops.autocast_state(x.device.type)
         dt = adt if on else self.compute_dtype
         if dt not in _MODES:
             raise NotImplementedError(f"NLayerDiscriminator: {_FP16_MSG}" if dt == torch.float16 else f"NLayerDiscriminator: compute dtype {dt}: float32 or bfloat16")
@@ -123,20 +115,7 @@ class NLayerDiscriminator(nn.Module):
 
     def _forward_pack(self, i, dt):
         """(packed rows, fp32 bias or None) of convolution i for vt_conv, repacked when the parameter's version changes"""
-        ly = self._layers[i]
-        return ly.pack.get(ly.conv.weight, ly.conv.bias, dt, cin_stored=8 if i == 0 else None)
-
-    def _dgrad_pack(self, i, dt):
-        ly = self._layers[i]
-        w = ly.conv.weight
-        key = (w.device, w._version, w.data_ptr())
-        ent = ly.dgrad.get(dt)
-        if ent is None or ent[0] != key:
-            wd = w.detach().float().contiguous()
-            cs = ops.pad_channels(ly.cout)
-            rows = ops.pack_conv_weight_dgrad(wd, dt, cs) if ly.geom.sh == 1 else ops.pack_conv_weight_dgrad_strided(wd, dt, ly.geom, cs)
-            ent = ly.dgrad[dt] = (key, rows)
-        return ent[1]
+        return self._layers[i].site.rows(dt, 8 if i == 0 else None)
 
     def _const(self, c, device):
         """(zeros, ones) fp32 [c]: the identity statistics of a layer without a norm"""
@@ -206,10 +185,9 @@ class NLayerDiscriminator(nn.Module):
 
     def forward_with_grad(self, x):
         """`forward(x)` attached to autograd: the same launches and the same bits, with every layer's input and convolution output kept for
-        a backward on the HIP kernels (vt_conv_dgrad, vt_conv_dgrad_strided, vt_conv_wgrad, vt_batchnorm_act_backward,
-        vt_leaky_relu_backward).  x.grad is filled when x requires grad (the generator step), the gradient of every parameter that
-        requires grad is filled (the discriminator step; a frozen parameter costs no launch).  With x detached and every parameter
-        frozen it returns the plain value."""
+        a backward on the HIP kernels (vt_conv_dgrad, vt_conv_wgrad, vt_batchnorm_act_backward, vt_leaky_relu_backward).  x.grad is
+        filled when x requires grad (the generator step), the gradient of every parameter that requires grad is filled (the
+        discriminator step; a frozen parameter costs no launch).  With x detached and every parameter frozen it returns the plain value."""
         dt = self._check(x, "forward_with_grad")
         params = [p for p in self.parameters() if p.requires_grad]
         if not torch.is_grad_enabled() or not (x.requires_grad or params):
@@ -248,11 +226,7 @@ class NLayerDiscriminator(nn.Module):
                     grads[ly.conv.bias] = dbias
             if not need_dx and not any(p.requires_grad for l2 in self._layers[:i] for p in _layer_params(l2)):
                 return None, grads
-            wt = self._dgrad_pack(i, dt)
-            if ly.geom.sh == 1:
-                d = ops.conv_dgrad(d, wt, ly.geom, cin=ly.cin, cout=ly.cout, dx_dtype=torch.float32)
-            else:
-                d = ops.conv_dgrad_strided(d, wt, ly.geom, cin=ly.cin, cout=ly.cout, in_hw=tuple(inp.shape[2:4]), dx_dtype=torch.float32)
+            d = ly.site.dgrad(d, in_hw=tuple(inp.shape[2:4]), dx_dtype=torch.float32)
         return ops.ndhwc_to_ncthw(d, self.input_nc).reshape(x_shape), grads
 
 

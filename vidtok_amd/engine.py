@@ -126,13 +126,7 @@ class AutoencodingEngine(nn.Module):
 
     def _sync_autocast(self, x):
         """make the arithmetic mode follow the caller's autocast context (device of `x`)"""
-        dev = x.device.type if isinstance(x, torch.Tensor) else "cuda"
-        try:
-            on = torch.is_autocast_enabled(dev)
-            adt = torch.get_autocast_dtype(dev) if on else None
-        except (TypeError, AttributeError, RuntimeError):      # older torch: the CUDA-only spellings
-            on = torch.is_autocast_enabled()
-            adt = torch.get_autocast_gpu_dtype() if on else None
+        on, adt = ops.autocast_state(x.device.type if isinstance(x, torch.Tensor) else "cuda")
         want = None
         if on:
             pol = self.autocast_policy.get({torch.bfloat16: "bfloat16", torch.float16: "float16"}.get(adt, ""), "error")

@@ -215,7 +215,7 @@ SIGNATURES = {
     "vt_layernorm_act_backward_work_bytes": (_I64, [_I64, _I32]),
     "vt_layernorm_act_backward": (C.c_int, [_P, _P, _I32, _I64, _P, _I32, _I64, _P, _P, _P, _P, _I64, _I32, _F, _I32, _P, _I64, _P]),
     "vt_dgrad_desc_size": (C.c_int, []),
-    "vt_pack_conv_weight_dgrad": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _P]),
+    "vt_pack_conv_weight_dgrad": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _P]),
     "vt_conv_dgrad_work_bytes": (_I64, [C.POINTER(DgradDesc)]),
     "vt_conv_dgrad": (C.c_int, [C.POINTER(DgradDesc), _P]),
     "vt_grad_fold": (C.c_int, [_P, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
@@ -233,9 +233,6 @@ SIGNATURES = {
     "vt_batchnorm_act_backward_work_bytes": (_I64, [_I64, _I32]),
     "vt_batchnorm_act_backward": (C.c_int, [_P, _P, _I32, _I32, _I64, _I64, _P, _I64, _P, _P, _P, _P, _F, _P, _P, _I64, _I32, _I32, _P, _I64, _P]),
     "vt_leaky_relu_backward": (C.c_int, [_P, _I32, _P, _P, _I32, _I64, _F, _P]),
-    "vt_pack_conv_weight_dgrad_strided": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _P]),
-    "vt_conv_dgrad_strided_work_bytes": (_I64, [C.POINTER(DgradDesc)]),
-    "vt_conv_dgrad_strided": (C.c_int, [C.POINTER(DgradDesc), _P]),
 }
 
 _lib = None

@@ -140,13 +140,7 @@ class LPIPS(nn.Module):
         return self
 
     def _dtype_now(self, x):
-        dev = x.device.type
-        try:
-            on = torch.is_autocast_enabled(dev)
-            adt = torch.get_autocast_dtype(dev) if on else None
-        except (TypeError, AttributeError, RuntimeError):
-            on = torch.is_autocast_enabled()
-            adt = torch.get_autocast_gpu_dtype() if on else None
+        on, adt = ops.autocast_state(x.device.type)
         if on:
             if adt not in (torch.bfloat16, torch.float16):
                 raise NotImplementedError(f"vidtok_amd LPIPS under torch.autocast(dtype={adt}): bfloat16 and float16 regions only")

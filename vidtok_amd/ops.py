@@ -98,6 +98,16 @@ def pad_channels(c: int) -> int:
     return (c + CH_ALIGN - 1) // CH_ALIGN * CH_ALIGN
 
 
+def autocast_state(device_type: str):
+    """(enabled, dtype or None) of the caller's torch.autocast region on `device_type`; what to do about it is the caller's policy"""
+    try:
+        on = torch.is_autocast_enabled(device_type)
+        return on, (torch.get_autocast_dtype(device_type) if on else None)
+    except (TypeError, AttributeError, RuntimeError):      # older torch: the CUDA-only spellings
+        on = torch.is_autocast_enabled()
+        return on, (torch.get_autocast_gpu_dtype() if on else None)
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -1014,40 +1024,50 @@ def layernorm_act_backward(y, dn, gamma, beta, *, silu: bool, eps: float = 1e-6,
 _GRAD_DT = (torch.float32, torch.bfloat16)
 
 
-def pack_conv_weight_dgrad(weight, dtype, cout_stored=None):
+def pack_conv_weight_dgrad(weight, dtype, cout_stored=None, geom: ConvGeom = None):
     """vt_pack_conv_weight_dgrad: weight fp32 [Cout, Cin, *k] on the GPU -> the rows [Cin, taps * cout_stored] vt_conv_dgrad convolves
-    dy with: taps flipped, Cin / Cout transposed, pad channels zero; `dtype` float32 or bfloat16"""
+    dy with: taps flipped, Cin / Cout transposed, pad channels zero; `dtype` float32 or bfloat16.  With `geom` (its strides and pads):
+    [sh * sw, Cin, ldw], per parity class of the input its flipped sub-kernel (packing.strided_dgrad_classes)"""
     lib = L.load()
     _chk(weight, "pack_dgrad.weight")
     assert weight.dtype == torch.float32 and weight.dim() >= 3 and dtype in _GRAD_DT
     cout, cin = weight.shape[:2]
     k3 = (1,) * (5 - weight.dim()) + tuple(weight.shape[2:]) if weight.dim() != 3 else (weight.shape[2], 1, 1)
+    assert geom is None or k3 == (geom.kt, geom.kh, geom.kw), (k3, geom)
+    sh, sw, ph, pw = (1, 1, 0, 0) if geom is None else (geom.sh, geom.sw, geom.ph, geom.pw)
     cout_p = cout_stored or pad_channels(cout)
-    ldw = k3[0] * k3[1] * k3[2] * cout_p
-    out = torch.empty((cin, ldw), dtype=dtype, device=weight.device)
-    L.check(lib.vt_pack_conv_weight_dgrad(_ptr(weight), _ptr(out), _DT[dtype], cout, cin, cout_p, k3[0], k3[1], k3[2], ldw, _stream()),
+    ldw = k3[0] * -(-k3[1] // sh) * -(-k3[2] // sw) * cout_p
+    out = torch.empty((cin, ldw) if geom is None else (sh * sw, cin, ldw), dtype=dtype, device=weight.device)
+    L.check(lib.vt_pack_conv_weight_dgrad(_ptr(weight), _ptr(out), _DT[dtype], cout, cin, cout_p, k3[0], k3[1], k3[2], sh, sw, ph, pw, ldw, _stream()),
             "vt_pack_conv_weight_dgrad")
     return out
 
 
-def conv_dgrad(dy, w, geom: ConvGeom, *, cin: int, cout: int, tmode=L.VT_TPAD_ZERO, acc=None, dx_dtype=None):
+def conv_dgrad(dy, w, geom: ConvGeom, *, cin: int, cout: int, tmode=L.VT_TPAD_ZERO, acc=None, dx_dtype=None, in_hw=None):
     """dx of `conv(x, ..., geom, cout=cout, tmode=tmode)` with respect to its stored input x [B, Ti, Hi, Wi, pad_channels(cin)] (in
     front of a folded nearest x2 up-sampling): dy [B, To, Ho, Wo, >= cout] fp32 or bf16, w = pack_conv_weight_dgrad(weight, dy.dtype,
-    dy.shape[-1]).  `acc` (dx's shape and dtype) is added: a residual junction costs no pass of its own.  dx_dtype: dy's (default) or
-    float32; a bf16 dx is the fp32 dx rounded once.  Stride-1 geometries only (vt_conv_dgrad)."""
+    dy.shape[-1]) -- with `geom` as well under a row / column stride of 2.  in_hw: the forward input's (Hi, Wi); required under a stride
+    (a strided output extent does not determine them), checked at stride 1.  `acc` (dx's shape and dtype) is added: a residual junction
+    costs no pass of its own.  dx_dtype: dy's (default) or float32; a bf16 dx is the fp32 dx rounded once (vt_conv_dgrad)."""
     lib = L.load()
     _chk(dy, "conv_dgrad.dy"); _chk(w, "conv_dgrad.w")
-    if (geom.st, geom.sh, geom.sw) != (1, 1, 1):
-        raise L.VtError(f"conv_dgrad: strides {(geom.st, geom.sh, geom.sw)}: only stride-1 convolutions have a data gradient here (the decoder has no strided one)")
     assert dy.dtype in _GRAD_DT and w.dtype == dy.dtype and dy.dim() == 5, (dy.dtype, w.dtype)
     dx_dtype = dx_dtype or dy.dtype
     B, To, Ho, Wo, lddy = dy.shape
-    # the input extents the forward convolution had (stride 1): inverse of ConvGeom.out_dims
-    Tv, Hv, Wv = To - geom.pt - geom.pt_hi + geom.kt - 1, Ho - geom.ph - geom.ph_hi + geom.kh - 1, Wo - geom.pw - geom.pw_hi + geom.kw - 1
-    assert Tv > 0 and Hv > 0 and Wv > 0 and Tv % (1 << geom.ups_t) == 0 and Hv % (1 << geom.ups_s) == 0 and Wv % (1 << geom.ups_s) == 0, (Tv, Hv, Wv)
-    Ti, Hi, Wi = Tv >> geom.ups_t, Hv >> geom.ups_s, Wv >> geom.ups_s
+    Tv = To - geom.pt - geom.pt_hi + geom.kt - 1
+    if (geom.st, geom.sh, geom.sw) == (1, 1, 1):
+        # the input extents the forward convolution had (stride 1): inverse of ConvGeom.out_dims
+        Hv, Wv = Ho - geom.ph - geom.ph_hi + geom.kh - 1, Wo - geom.pw - geom.pw_hi + geom.kw - 1
+        assert Tv > 0 and Hv > 0 and Wv > 0 and Tv % (1 << geom.ups_t) == 0 and Hv % (1 << geom.ups_s) == 0 and Wv % (1 << geom.ups_s) == 0, (Tv, Hv, Wv)
+        Hi, Wi = Hv >> geom.ups_s, Wv >> geom.ups_s
+        assert in_hw is None or tuple(in_hw) == (Hi, Wi), (in_hw, Hi, Wi)
+    elif in_hw is None:
+        raise L.VtError(f"conv_dgrad: strides {(geom.st, geom.sh, geom.sw)}: a strided output extent does not determine the input's: pass in_hw")
+    else:
+        Hi, Wi = in_hw
+    Ti = Tv >> geom.ups_t
     ldx = pad_channels(cin)
-    assert tuple(w.shape) == (cin, geom.kt * geom.kh * geom.kw * lddy), (tuple(w.shape), cin, lddy)
+    w = w.unsqueeze(0) if w.dim() == 2 else w
     d = L.DgradDesc()
     d.dy, d.wt = dy.data_ptr(), w.data_ptr()
     d.B, d.Ti, d.Hi, d.Wi, d.lddx, d.Cin = B, Ti, Hi, Wi, ldx, cin
@@ -1055,7 +1075,7 @@ def conv_dgrad(dy, w, geom: ConvGeom, *, cin: int, cout: int, tmode=L.VT_TPAD_ZE
     d.KT, d.KH, d.KW, d.st, d.sh, d.sw = geom.kt, geom.kh, geom.kw, geom.st, geom.sh, geom.sw
     d.pt, d.ph, d.pw, d.pt_hi, d.ph_hi, d.pw_hi = geom.pt, geom.ph, geom.pw, geom.pt_hi, geom.ph_hi, geom.pw_hi
     d.tmode, d.ups_t, d.ups_s, d.dtype, d.dx_dtype = tmode, geom.ups_t, geom.ups_s, _DT[dy.dtype], _DT.get(dx_dtype, -1)
-    d.ldw = w.shape[1]
+    d.ldw = w.shape[2]
     if acc is not None:
         _chk(acc, "conv_dgrad.acc")
         assert acc.dtype == dx_dtype and tuple(acc.shape) == (B, Ti, Hi, Wi, ldx), (acc.dtype, tuple(acc.shape))
@@ -1063,6 +1083,7 @@ def conv_dgrad(dy, w, geom: ConvGeom, *, cin: int, cout: int, tmode=L.VT_TPAD_ZE
     nb = lib.vt_conv_dgrad_work_bytes(C.byref(d))
     if nb < 0:
         L.check(-1, "vt_conv_dgrad_work_bytes")
+    assert tuple(w.shape) == (geom.sh * geom.sw, cin, -(-geom.kh // geom.sh) * -(-geom.kw // geom.sw) * geom.kt * lddy), (tuple(w.shape), cin, lddy)
     # a launch that writes dx from the convolution's epilogue leaves the pad lanes alone: they are zeroed here
     dx = (torch.empty if (nb > 0 or ldx == cin) else torch.zeros)((B, Ti, Hi, Wi, ldx), dtype=dx_dtype, device=dy.device)
     d.dx = dx.data_ptr()
@@ -1228,7 +1249,7 @@ def lpips_prep_backward(d, scale):
     return out
 
 
-# ---- PatchGAN discriminator (include/vidtok_amd.h: vt_batchnorm_*, vt_leaky_relu_backward, vt_conv_dgrad_strided) ----------------------
+# ---- PatchGAN discriminator (include/vidtok_amd.h: vt_batchnorm_*, vt_leaky_relu_backward) ---------------------------------------------
 def batchnorm_stats(x, c: int = None, eps: float = 1e-5):
     """vt_batchnorm_stats over the rows of x [..., ld] (fp32 or bf16): (mean, biased var, rstd = 1 / sqrt(var + eps)), fp32 [c] each"""
     lib = L.load()
@@ -1297,57 +1318,4 @@ def leaky_relu_backward(dy, y, slope: float):
     assert dy.shape == y.shape and y.dtype in _GRAD_DT and dy.dtype in (y.dtype, torch.float32), (tuple(dy.shape), tuple(y.shape), dy.dtype, y.dtype)
     dx = torch.empty_like(y)
     L.check(lib.vt_leaky_relu_backward(_ptr(dy), _DT[dy.dtype], _ptr(y), _ptr(dx), _DT[y.dtype], y.numel(), float(slope), _stream()), "vt_leaky_relu_backward")
-    return dx
-
-
-def pack_conv_weight_dgrad_strided(weight, dtype, geom: ConvGeom, cout_stored=None):
-    """vt_pack_conv_weight_dgrad_strided: weight fp32 [Cout, Cin, *k] on the GPU -> [sh * sw, Cin, ldw]: per parity class of the input the
-    flipped, transposed sub-kernel vt_conv_dgrad_strided convolves dy with (packing.strided_dgrad_classes)"""
-    lib = L.load()
-    _chk(weight, "pack_dgrad_strided.weight")
-    assert weight.dtype == torch.float32 and weight.dim() in (4, 5) and dtype in _GRAD_DT
-    cout, cin = weight.shape[:2]
-    kt, kh, kw = (1,) * (5 - weight.dim()) + tuple(weight.shape[2:])
-    assert (kt, kh, kw) == (geom.kt, geom.kh, geom.kw), ((kt, kh, kw), geom)
-    cout_p = cout_stored or pad_channels(cout)
-    ldw = kt * -(-kh // geom.sh) * -(-kw // geom.sw) * cout_p
-    out = torch.empty((geom.sh * geom.sw, cin, ldw), dtype=dtype, device=weight.device)
-    L.check(lib.vt_pack_conv_weight_dgrad_strided(_ptr(weight), _ptr(out), _DT[dtype], cout, cin, cout_p, kt, kh, kw, geom.sh, geom.sw, geom.ph, geom.pw, ldw,
-                                                  _stream()), "vt_pack_conv_weight_dgrad_strided")
-    return out
-
-
-def conv_dgrad_strided(dy, w, geom: ConvGeom, *, cin: int, cout: int, in_hw, acc=None, dx_dtype=None):
-    """dx of `conv(x, ..., geom, cout=cout)` with row / column stride 2 with respect to its stored input x [B, Ti, in_hw[0], in_hw[1],
-    pad_channels(cin)]: dy [B, To, Ho, Wo, >= cout] fp32 or bf16, w = pack_conv_weight_dgrad_strided(weight, dy.dtype, geom, dy.shape[-1]).
-    in_hw: the forward input's (Hi, Wi) -- a strided output extent does not determine them.  acc / dx_dtype as conv_dgrad."""
-    lib = L.load()
-    _chk(dy, "conv_dgrad_strided.dy"); _chk(w, "conv_dgrad_strided.w")
-    assert dy.dtype in _GRAD_DT and w.dtype == dy.dtype and dy.dim() == 5 and w.dim() == 3, (dy.dtype, w.dtype)
-    dx_dtype = dx_dtype or dy.dtype
-    B, To, Ho, Wo, lddy = dy.shape
-    Hi, Wi = in_hw
-    Ti = To - geom.pt - geom.pt_hi + geom.kt - 1
-    ldx = pad_channels(cin)
-    d = L.DgradDesc()
-    d.dy, d.wt = dy.data_ptr(), w.data_ptr()
-    d.B, d.Ti, d.Hi, d.Wi, d.lddx, d.Cin = B, Ti, Hi, Wi, ldx, cin
-    d.To, d.Ho, d.Wo, d.lddy, d.Cout = To, Ho, Wo, lddy, cout
-    d.KT, d.KH, d.KW, d.st, d.sh, d.sw = geom.kt, geom.kh, geom.kw, geom.st, geom.sh, geom.sw
-    d.pt, d.ph, d.pw, d.pt_hi, d.ph_hi, d.pw_hi = geom.pt, geom.ph, geom.pw, geom.pt_hi, geom.ph_hi, geom.pw_hi
-    d.tmode, d.ups_t, d.ups_s, d.dtype, d.dx_dtype = L.VT_TPAD_ZERO, geom.ups_t, geom.ups_s, _DT[dy.dtype], _DT.get(dx_dtype, -1)
-    d.ldw = w.shape[2]
-    if acc is not None:
-        _chk(acc, "conv_dgrad_strided.acc")
-        assert acc.dtype == dx_dtype and tuple(acc.shape) == (B, Ti, Hi, Wi, ldx), (acc.dtype, tuple(acc.shape))
-        d.acc, d.ldacc = acc.data_ptr(), ldx
-    nb = lib.vt_conv_dgrad_strided_work_bytes(C.byref(d))
-    if nb < 0:
-        L.check(-1, "vt_conv_dgrad_strided_work_bytes")
-    assert tuple(w.shape[:2]) == (geom.sh * geom.sw, cin), (tuple(w.shape), cin)
-    dx = torch.empty((B, Ti, Hi, Wi, ldx), dtype=dx_dtype, device=dy.device)
-    d.dx = dx.data_ptr()
-    work = torch.empty((max(nb, 16),), dtype=torch.uint8, device=dy.device)
-    d.work, d.work_bytes = work.data_ptr(), nb
-    L.check(lib.vt_conv_dgrad_strided(C.byref(d), _stream()), "vt_conv_dgrad_strided")
     return dx

@@ -186,11 +186,12 @@ class PackedCache:
 
 
 class DgradPackCache:
-    """The transposed, tap-flipped rows vt_conv_dgrad convolves dy with (ops.pack_conv_weight_dgrad), cached per parameter version like
-    PackedCache: an optimizer step bumps `weight._version` and the next backward packs again.  GPU parameters only (the backward has
-    no host form)."""
+    """The transposed, tap-flipped rows vt_conv_dgrad convolves dy with (ops.pack_conv_weight_dgrad: one block per parity class of the
+    geometry's strides), cached per parameter version like PackedCache: an optimizer step bumps `weight._version` and the next backward
+    packs again.  GPU parameters only (the backward has no host form)."""
 
-    def __init__(self):
+    def __init__(self, geom):
+        self._geom = {} if (geom.sh, geom.sw) == (1, 1) else {"geom": geom}      # stride 1: the plain rows [Cin, ldw]
         self._entries = {}           # (dtype, cout_stored) -> (validity key, rows)
 
     def get(self, weight: torch.nn.Parameter, dtype, cout_stored):
@@ -200,7 +201,7 @@ class DgradPackCache:
         if ent is None or ent[0] != key:
             wd = weight.detach()
             wd = wd if wd.dtype == torch.float32 and wd.is_contiguous() else wd.float().contiguous()
-            ent = self._entries[slot] = (key, ops.pack_conv_weight_dgrad(wd, dtype, cout_stored))
+            ent = self._entries[slot] = (key, ops.pack_conv_weight_dgrad(wd, dtype, cout_stored, **self._geom))
         return ent[1]
 
 
@@ -231,11 +232,17 @@ class ConvSite:
 
     def dgrad_rows(self, dtype, cout_stored):
         if self._dgrad is None:
-            self._dgrad = DgradPackCache()
+            self._dgrad = DgradPackCache(self.geom)
         return self._dgrad.get(self.conv.weight, dtype, cout_stored)
 
+    def dgrad(self, dy, *, in_hw=None, **kw):
+        """dx of the site's convolution on a whole clip (ops.conv_dgrad); in_hw: the input's (Hi, Wi), read under a stride only"""
+        if (self.geom.sh, self.geom.sw) != (1, 1):
+            kw["in_hw"] = in_hw
+        return ops.conv_dgrad(dy, self.dgrad_rows(dy.dtype, dy.shape[-1]), self.geom, cin=self.cin, cout=self.cout, tmode=self.clip_tmode, **kw)
 
-# ---- parity classes of a strided convolution's data gradient (vt_conv_dgrad_strided, include/vidtok_amd.h) ----------------------------
+
+# ---- parity classes of a convolution's data gradient (vt_conv_dgrad, include/vidtok_amd.h) --------------------------------------------
 def strided_axis_class(k: int, s: int, p: int, r: int, extent: int = None) -> dict:
     """one axis of a parity class: input positions i = s j + r receive the taps k0, k0 + s, ... (those with (r + p - tap) mod s = 0)
     from dy[j + (r + p) // s - m] for the m-th of them.  As a stride-1 convolution over dy that is the flipped tap list under the front
@@ -250,7 +257,7 @@ def strided_axis_class(k: int, s: int, p: int, r: int, extent: int = None) -> di
 
 
 def strided_dgrad_classes(kh: int, kw: int, sh: int, sw: int, ph: int, pw: int, hi: int = None, wi: int = None) -> list:
-    """the class table of vt_conv_dgrad_strided, class rh * sw + rw at index rh * sw + rw: [(rows, cols)] of strided_axis_class.  Every
-    forward tap (p, q) appears in exactly one class; a class with an empty tap list is zeros; a negative pad is a geometry the entry
-    point refuses."""
+    """the class table of vt_conv_dgrad, class rh * sw + rw at index rh * sw + rw: [(rows, cols)] of strided_axis_class.  Every forward
+    tap (p, q) appears in exactly one class (stride 1: the one class holds them all, flipped, under the mirrored pads K - 1 - p); a
+    negative pad -- every class with an empty tap list (K < s) has one -- is a geometry the entry point refuses."""
     return [(strided_axis_class(kh, sh, ph, rh, hi), strided_axis_class(kw, sw, pw, rw, wi)) for rh in range(sh) for rw in range(sw)]

@@ -791,6 +791,53 @@ def test_model_handle_tiled_matches_engine(name, shape, tc, overlap, dtype):
         lib.vt_destroy(h)
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, X3], ids=["bf16", "bf16x3"])
+def test_model_handle_repacks_after_weight_reload(dtype):
+    """vt_load_weight on a handle that has already packed and used its weights: every packed form of the replaced tensor is dropped and
+    packed again from the new values -- the plain rows of conv_in, the several forms one time up-sampler's key has (parity classes, or
+    the U and V of the three-product form), the four parity classes of a spatial up-sampler, a LayerNorm affine.  The decode after the
+    reload gives the bits of the engine after the same load_state_dict."""
+    import ctypes as C
+
+    from vidtok_amd import lib as L
+    from vidtok_amd import ops
+
+    model, cfg, sd = build_model("vidtok_kl_causal_488_4chn", device=DEV, dtype=dtype)
+    lib = L.load()
+    h, mc = _make_handle(L, lib, cfg, sd, dtype)          # loads every weight, then vt_prepare
+    try:
+        B, T, H, W = 1, 5, 64, 64
+        torch.manual_seed(8)
+        x = (torch.rand((B, 3, T, H, W), device=DEV) * 2 - 1).contiguous()
+        z = ops.kl_sample(model._run_encoder(x).contiguous(), None)[0].contiguous()
+        nbytes = lib.vt_workspace_bytes(h, B, T, H, W)
+        assert nbytes > 0, lib.vt_last_error()
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def decode():
+            ref = model._run_decoder(z)
+            got = torch.empty_like(ref)
+            L.check(lib.vt_decode(h, z.data_ptr(), B, z.shape[2], z.shape[3], z.shape[4], got.data_ptr(), ws.data_ptr(), nbytes, st), "vt_decode")
+            torch.cuda.synchronize()
+            assert torch.equal(got, ref), f"decoder: {rel_err(got, ref):.3e}"
+            return ref
+
+        first = decode()
+        keys = ["decoder.conv_in.conv.weight", "decoder.up_temporal.2.upsample.conv.conv.weight", "decoder.up.1.upsample.conv.weight",
+                "decoder.norm_out.norm.weight"]
+        sd2 = dict(sd)
+        for i, k in enumerate(keys):
+            g = torch.Generator().manual_seed(900 + i)
+            sd2[k] = sd[k] * (1 + 0.25 * torch.randn(sd[k].shape, generator=g))
+            t = sd2[k].detach().float().contiguous().cpu()
+            L.check(lib.vt_load_weight(h, k.encode(), t.data_ptr(), (C.c_int64 * t.dim())(*t.shape), t.dim()), "vt_load_weight")
+        model.load_state_dict(sd2, strict=True)
+        assert not torch.equal(decode(), first), "the reloaded tensors change the reconstruction"
+    finally:
+        lib.vt_destroy(h)
+
+
 def test_model_handle_tiling_refused_for_v10():
     import ctypes as C
 

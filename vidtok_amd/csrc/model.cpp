@@ -14,6 +14,11 @@
 // (version 2) the non-causal family, Encoder3D / Decoder3D of model_3dnoncausal.py:314-651: the same stages with centred temporal
 // windows and plain nn.Conv parameter keys.
 //
+// The vocabulary is the Python host's: a `Site` is one convolution as the kernels see it (packing.ConvSite: key, window, weight
+// transform, chunk state; built once by the graph builders, which is where the parameter list comes from), `residual_block` the one
+// body of the residual stages, `keep_frames` the one way a module keeps frames as its chunk cache, `guarded` the one exception
+// boundary of the extern "C" entries.
+//
 // Memory: weights are packed on the host when first used and live in device allocations owned by the handle;
 // activations come from a caller-provided workspace, cut into two arenas that alternate between stages (a stage reads the
 // previous stage's output from one arena and builds its own output and temporaries in the other);
@@ -59,6 +64,21 @@ struct Fail {
       throw Fail{VT_ERR_HIP};                                              \
     }                                                                      \
   } while (0)
+
+// the body of an extern "C" entry: a Fail becomes its code, any other exception "<name>: what()" + VT_ERR_ARG; the int64_t flavour
+// (the *_bytes entries) answers -1 for both
+template <class F>
+auto guarded(const char* name, F&& body) -> decltype(body()) {
+  const bool bytes = sizeof(decltype(body())) == sizeof(int64_t);
+  try {
+    return body();
+  } catch (const Fail& f) {
+    return bytes ? -1 : f.code;
+  } catch (const std::exception& e) {
+    vt_set_error("%s: %s", name, e.what());
+    return bytes ? -1 : VT_ERR_ARG;
+  }
+}
 
 int pad8(int c) { return (c + 7) / 8 * 8; }
 size_t esize(int dt) { return dt == VT_F32 ? 4 : 2; }
@@ -171,8 +191,6 @@ struct Model {
   bool x3 = false;                 // VT_BF16X3: fp32 storage, convolutions on split-bf16 weight planes (three bf16 MFMAs per product)
   bool v11() const { return cfg.version == 1; }
   bool noncausal() const { return cfg.version == 2; }          // Encoder3D / Decoder3D of model_3dnoncausal.py: centred temporal windows
-  // the parameter level a Causal* wrapper adds in front of its nn.Conv ("...conv1.conv.weight"); plain nn.Conv3d / Conv1d have none
-  std::string cv() const { return noncausal() ? "" : ".conv"; }
   // time padding of a convolution with taps before the clip: zeros (v1.0) or the first frame repeated (v1.1, one pass)
   int tpad() const { return v11() ? VT_TPAD_REPLICATE : VT_TPAD_ZERO; }
   std::map<std::string, Param> params;
@@ -213,27 +231,32 @@ struct Model {
     return p;
   }
   // fp32 vector on the device as it is (biases, LayerNorm affines, mix factors)
-  const float* f32(const std::string& key, bool dry) {
+  static std::string f32_ckey(const std::string& key) { return "f32:" + key; }
+  const float* f32(const std::string& key, bool dry) { return f32(key, f32_ckey(key), dry); }
+  const float* f32(const std::string& key, const std::string& ckey, bool dry) {
     if (dry && !prepare) {
       expected.push_back(key);
       return nullptr;
     }
-    auto it = packed.find("f32:" + key);
+    auto it = packed.find(ckey);
     if (it != packed.end()) return (const float*)it->second->p;
     const Param& p = param(key);
-    return (const float*)upload("f32:" + key, p.data.data(), p.data.size() * 4);
+    return (const float*)upload(ckey, p.data.data(), p.data.size() * 4);
   }
   // convolution weight [Cout][Cin][k...] -> [Cout][taps * cin_p] in the arithmetic dtype (vidtok_amd/packing.py); `xf`
   // optionally rewrites the fp32 weight first (parity classes of the up-samplers: pre-summed taps)
   typedef std::vector<float> (*Xform)(const Param&, std::vector<int64_t>& shape, int a, int b);
-  // `rows` = plain rows in the storage type even under VT_BF16X3 (the row operand of a GEMM against activations)
-  const void* conv_w(const std::string& key, int cin_p, bool dry, Xform xf = nullptr, int xa = 0, int xb = 0, bool rows = false) {
+  // `rows` = plain rows in the storage type even under VT_BF16X3 (the row operand of a GEMM against activations).  `ckey` names
+  // the packed form in `packed` (w_ckey: a Site builds it once; vt_load_weight drops every "w:<key>:..." of the tensor it replaces)
+  std::string w_ckey(const std::string& key, int cin_p, Xform xf, int xa, int xb, bool rows) const {
+    return "w:" + key + ":" + std::to_string(cin_p) + ":" + std::to_string(dt) + (x3 && !rows ? "x3" : "") + ":" + std::to_string((xf ? 1 : 0) * 100 + xa * 10 + xb);
+  }
+  const void* conv_w(const std::string& key, const std::string& ckey, int cin_p, bool dry, Xform xf, int xa, int xb, bool rows) {
     if (dry && !prepare) {
       expected.push_back(key);
       return nullptr;
     }
     const bool split = x3 && !rows;
-    const std::string ckey = "w:" + key + ":" + std::to_string(cin_p) + ":" + std::to_string(dt) + (split ? "x3" : "") + ":" + std::to_string((xf ? 1 : 0) * 100 + xa * 10 + xb);
     auto it = packed.find(ckey);
     if (it != packed.end()) return it->second->p;
     const Param& p = param(key);
@@ -301,7 +324,7 @@ std::vector<float> xf_time_parity(const Param& p, std::vector<int64_t>& shape, i
 }
 // the three-product form of the causal time up-sampler (packing.py::time_upsample3_weights): part 2 = [W0, W2] (the k = 2 window of U),
 // part 3 = W1 alone (V, a per-frame convolution); single taps, nothing summed.  (The part numbers continue xf_time_parity's 0 / 1:
-// conv_w keys a packed weight by the transform's arguments.)
+// Model::w_ckey names a packed weight by the transform's arguments.)
 std::vector<float> xf_time_up3(const Param& p, std::vector<int64_t>& shape, int part, int) {
   const int64_t co = shape[0], ci = shape[1], hw = shape[3] * shape[4];
   const int kt = part == 2 ? 2 : 1;
@@ -517,67 +540,132 @@ Act conv(Ctx& c, const Tens& x, const void* w, int ldw, const float* bias, const
   return r;
 }
 
-// frames idx[0..n) of src [B][Ts][frame] -> dst frames [t0, t0 + n) of [B][Td][frame] (vidtok_amd/ops.py::gather_frames)
-void gather(Ctx& c, const char* src, int Ts, char* dst, int Td, int t0, const std::vector<int>& idx, int B, int64_t frame_elems, int es) {
+std::vector<int> range(int a, int b) {                 // a, a + 1, ..., b - 1
+  std::vector<int> v;
+  for (int t = a; t < b; ++t) v.push_back(t);
+  return v;
+}
+Tens frames_at(const Tens& like, const void* p, int T) {          // T frames shaped like `like`'s at p
+  Tens t = like;
+  t.p = (char*)p;
+  t.T = T;
+  return t;
+}
+
+// frames idx[0..n) of src -> dst frames [t0, t0 + n) of [B][Td][frame] (vidtok_amd/ops.py::gather_frames)
+void gather(Ctx& c, const Tens& src, char* dst, int Td, int t0, const std::vector<int>& idx) {
+  const int64_t fr = (int64_t)src.H * src.W * src.ld;
+  const int es = (int)esize(src.dt);
   for (size_t j0 = 0; j0 < idx.size(); j0 += 128) {
     int32_t part[128];
     const int n = (int)std::min<size_t>(128, idx.size() - j0);
     for (int j = 0; j < n; ++j) part[j] = idx[j0 + j];
-    if (!c.dry)
-      M_CALL(vt_gather_frames(src, dst + (size_t)(t0 + (int)j0) * frame_elems * es, es, B, frame_elems, (int64_t)Ts * frame_elems, (int64_t)Td * frame_elems, part, n, c.stream));
+    if (!c.dry) M_CALL(vt_gather_frames(src.p, dst + (size_t)(t0 + (int)j0) * fr * es, es, src.B, fr, (int64_t)src.T * fr, (int64_t)Td * fr, part, n, c.stream));
   }
+}
+
+// keep frames idx of src as st's chunk cache: frames [t0, t0 + n) of the `total` (default: n) the cache then holds
+void keep_frames(Ctx& c, CState& st, const Tens& src, const std::vector<int>& idx, int t0 = 0, int total = 0) {
+  if (total == 0) total = (int)idx.size();
+  char* buf = c.m->persistent(st, frames_at(src, nullptr, total).bytes(), c.dry);
+  gather(c, src, buf, total, t0, idx);
+  if (!c.dry) st.frames = total;
 }
 
 // _CausalState._update_cache (vidtok_amd/modules.py; reference model_3dcausal_v1_1.py:172-176): keep the last P frames of
 // padded[: len - offset], padded = [P pad frames (x[0] repeated on the first chunk | the previous cache), x]
 void update_cache(Ctx& c, CState& st, const Tens& x, int P) {
   if (P == 0) return;
-  Model* m = c.m;
-  const int T = x.T, off = st.offset, es = (int)esize(x.dt);
-  const int64_t fr = (int64_t)x.H * x.W * x.ld;
-  std::vector<int> sx, sc;
-  int jx = -1, jc = -1;
+  const int T = x.T, off = st.offset;
+  std::vector<int> sx, sc;                           // the frames taken from x, and in front of them those that stay from the old cache
   for (int j = 0; j < P; ++j) {
     const int q = T - off + j;                      // index into the padded sequence
     M_CHECK(q >= 0, "vt_model: chunk of %d frames is shorter than its cache offset %d", T, off);
-    if (q >= P) { if (jx < 0) jx = j; sx.push_back(q - P); }
-    else if (m->first_chunk) { if (jx < 0) jx = j; sx.push_back(0); }
-    else { if (jc < 0) jc = j; sc.push_back(q); }
+    if (q >= P) sx.push_back(q - P);
+    else if (c.m->first_chunk) sx.push_back(0);
+    else sc.push_back(q);
   }
   // frames kept from the old cache move inside the buffer they are read from: through a temporary (stream order)
-  char* kept = nullptr;
   if (!sc.empty()) {
     M_CHECK(c.dry || st.frames >= P, "vt_model: causal cache missing (the first chunk must come first)");
-    kept = c.cur->alloc((size_t)x.B * sc.size() * fr * es, c.dry);
-    gather(c, c.dry ? nullptr : (const char*)st.buf->p, P, kept, (int)sc.size(), 0, sc, x.B, fr, es);
+    const Tens kept = c.alloc(x.B, (int)sc.size(), x.H, x.W, x.ld, x.dt, x.ld);
+    gather(c, frames_at(x, c.dry ? nullptr : st.buf->p, P), kept.p, kept.T, 0, sc);
+    keep_frames(c, st, kept, range(0, kept.T), 0, P);
   }
-  char* buf = m->persistent(st, (size_t)x.B * P * fr * es, c.dry);
-  if (kept) {
-    std::vector<int> id(sc.size());
-    for (size_t i = 0; i < id.size(); ++i) id[i] = (int)i;
-    gather(c, kept, (int)sc.size(), buf, P, jc, id, x.B, fr, es);
-  }
-  if (!sx.empty()) gather(c, x.p, T, buf, P, jx, sx, x.B, fr, es);
-  if (!c.dry) st.frames = P;
+  if (!sx.empty()) keep_frames(c, st, x, sx, (int)sc.size(), P);
 }
 
-// a causal convolution with chunk state: CausalConv3d.run / CausalConv1d.run of vidtok_amd/modules.py
-Act conv_causal(Ctx& c, CState& st, const Tens& x, const void* w, int ldw, const float* bias, const Geom& g, int cout, ConvOpts o) {
-  Model* m = c.m;
-  const int P = g.pt;
-  if (m->tiled && P > 0) {
-    if (m->first_chunk) o.tmode = VT_TPAD_REPLICATE;
-    else {
-      M_CHECK(c.dry || st.frames >= P, "vt_model: causal cache missing (the first chunk must come first)");
-      o.tmode = VT_TPAD_CACHE;
-      o.cache = c.dry ? (const void*)16 : st.buf->p;
-      o.ncache = c.dry ? P : st.frames;
-    }
+typedef std::map<std::string, std::vector<int64_t>> Shapes;     // reference state_dict key -> parameter shape
+struct Build {                     // what the graph builders pass around: the handle being built and its parameter list
+  Model& m;
+  Shapes& sh;
+  const vt_model_config& cf() const { return m.cfg; }
+  bool wrap() const { return !m.noncausal(); }                   // the causal families keep their 3-D / 1-D convolutions under a Causal* wrapper
+  int gn_site() const { return wrap() ? VT_GN_FRAME : VT_GN_CLIP; }      // the view the 3-D sites hand to GroupNorm (vidtok_amd/modules.py SITE_*)
+  // a norm of the graph under `key` over `ch` channels; `site` = the view its call site hands to GroupNorm
+  void norm(Norm& n, const std::string& key, int ch, int site) {
+    n.key = key;
+    n.group = cf().norm_type == 1;
+    n.site = site;
+    sh[n.wkey()] = {ch};
+    sh[n.bkey()] = {ch};
   }
-  const Act r = conv(c, x, w, ldw, bias, g, cout, o);
-  if (m->tiled) update_cache(c, st, x, P);
-  return r;
-}
+};
+
+// One convolution as the kernels see it (packing.ConvSite of the Python host): its parameters' state_dict key, its window, the
+// transform that turns the stored weight into this launch's operand, and -- causal sites -- its chunk state.  Built once by the
+// graph builders, which is also where its parameters enter the handle's list; several sites may read one key (the parity classes
+// of the up-samplers, the U and V forms of the three-product time up-sampler).
+struct Site {
+  std::string wkey, bkey;          // "<key>.weight" / "<key>.bias"
+  std::string wckey, bckey;        // their packed forms in Model::packed
+  int cin = 0, cout = 0;
+  Geom g;
+  Model::Xform xf = nullptr;       // parity classes: pre-summed taps (xf_* above) with arguments xa, xb
+  int xa = 0, xb = 0;
+  bool rows = false;               // plain rows even under VT_BF16X3 (attention's W_v)
+  bool causal = false;             // keeps `st` in a tiled pass (CausalConv3d.run / CausalConv1d.run of vidtok_amd/modules.py)
+  CState st;
+  // `k`: the kernel dims of the stored tensor.  THE key rule: a convolution with a time axis sits under a Causal* wrapper, which
+  // adds a ".conv" level ("...conv1.conv.weight"), in the causal families; nn.Conv2d and the non-causal family's nn.Conv3d / Conv1d have none
+  void init(Build& b, const std::string& key, int cout_, int cin_, std::vector<int64_t> k, const Geom& g_, bool causal_ = false,
+            Model::Xform xf_ = nullptr, int xa_ = 0, int xb_ = 0, bool rows_ = false) {
+    const std::string full = key + (b.wrap() && k.size() != 2 ? ".conv" : "");
+    cin = cin_; cout = cout_; g = g_; causal = causal_; xf = xf_; xa = xa_; xb = xb_; rows = rows_;
+    wkey = full + ".weight"; bkey = full + ".bias";
+    wckey = b.m.w_ckey(wkey, pad8(cin), xf, xa, xb, rows); bckey = Model::f32_ckey(bkey);
+    std::vector<int64_t> w = {cout, cin};
+    w.insert(w.end(), k.begin(), k.end());
+    b.sh[wkey] = w;
+    b.sh[bkey] = {cout};
+  }
+  const void* w(Ctx& c) const { return c.m->conv_w(wkey, wckey, pad8(cin), c.dry, xf, xa, xb, rows); }
+  const float* bias(Ctx& c) const { return c.m->f32(bkey, bckey, c.dry); }
+  int ldw(const Tens& x) const { return g.kt * g.kh * g.kw * x.ld; }
+  Act run(Ctx& c, const Tens& x, ConvOpts o, bool with_bias = true) {
+    const int P = g.pt;
+    const bool cached = causal && c.m->tiled;
+    if (cached && P > 0) {
+      if (c.m->first_chunk) o.tmode = VT_TPAD_REPLICATE;
+      else {
+        M_CHECK(c.dry || st.frames >= P, "vt_model: causal cache missing (the first chunk must come first)");
+        o.tmode = VT_TPAD_CACHE;
+        o.cache = c.dry ? (const void*)16 : st.buf->p;
+        o.ncache = c.dry ? P : st.frames;
+      }
+    }
+    const Act r = conv(c, x, w(c), ldw(x), with_bias ? bias(c) : nullptr, g, cout, o);
+    if (cached) update_cache(c, st, x, P);
+    return r;
+  }
+  // launch nothing; answer whether the epilogue would take o.ln (Act::has_n; o.ln_optional) and, `tup3` (asked before any weight is
+  // packed: stand-in operands), whether vt_time_upsample3 serves the descriptor (Act::tup3)
+  Act probe(Ctx& c, const Tens& x, ConvOpts o, bool tup3 = false) {
+    o.plan_only = true;
+    o.tup3_probe = tup3;
+    return conv(c, x, tup3 ? (const void*)16 : w(c), ldw(x), tup3 ? nullptr : bias(c), g, cout, o);
+  }
+};
 
 // batched C[z] = A[z] B[z]^T on the convolution kernel (vidtok_amd/ops.py::gemm_nt)
 char* gemm_nt(Ctx& c, const void* a, bool a_batched, const void* b, int Z, int M, int N, int K, int in_dt, int out_dt, int ldo, const float* bias) {
@@ -614,65 +702,70 @@ ConvOpts emit(NormRef next, int tmode = VT_TPAD_ZERO) {
   return o;
 }
 
-struct ConvParams {                // an nn.ConvNd parameter pair under `key` (".weight" / ".bias")
-  std::string key;
-  int cin = 0, cout = 0;
-};
+// the body of every residual block (residual_block of the Python host): norm1 + SiLU -> conv1, seen only through norm2 + SiLU ->
+// [1x1 shortcut of x] -> conv2 + residual, emitting the consumer's norm
+Act residual_block(Ctx& c, const Norm& n1, const Norm& n2, Site& c1, Site& c2, Site* shortcut, const Act& x, NormRef next) {
+  const Tens h = n1.apply(c, x, true, c1.cin);
+  ConvOpts o1;
+  o1.ln = NormRef{&n2, true};
+  o1.keep_y = false;
+  o1.tmode = c.m->tpad();
+  const Act h2 = c1.run(c, h, o1);
+  const Tens xs = shortcut ? shortcut->run(c, x.y, ConvOpts()).y : x.y;
+  ConvOpts o2 = emit(next, c.m->tpad());
+  o2.res = &xs;
+  o2.res_mode = VT_RES_ADD;
+  return c2.run(c, h2.n, o2);
+}
 
 struct ResBlock : Stage {          // ResnetBlock (2-D per frame) or ResnetCausalBlock (3-D causal), model_3dcausal.py:276-424
-  bool causal3d_ = false;
-  int cin, cout;
   Norm n1, n2;
-  ConvParams c1, c2, sc;
-  CState s1, s2;                   // the 3-D causal block's convolutions keep two frames each in a tiled pass
+  Site c1, c2, sc;                 // the 3-D causal block's convolutions keep two frames each in a tiled pass; sc: nin_shortcut, where cin != cout
+  ResBlock(Build& b, const std::string& key, int cin, int cout, bool causal, int site = VT_GN_FRAME) {
+    Geom g3 = causal ? causal3d(3, 3, 3) : causal3d(1, 3, 3);
+    if (causal && b.m.noncausal()) g3 = centred(g3, 1);             // ResnetNoncausalBlock: Conv3d padding 1
+    const std::vector<int64_t> k3 = causal ? std::vector<int64_t>{3, 3, 3} : std::vector<int64_t>{3, 3};
+    b.norm(n1, key + ".norm1", cin, site);
+    b.norm(n2, key + ".norm2", cout, site);
+    c1.init(b, key + ".conv1", cout, cin, k3, g3, causal);
+    c2.init(b, key + ".conv2", cout, cout, k3, g3, causal);
+    if (cin != cout) sc.init(b, key + ".nin_shortcut", cout, cin, std::vector<int64_t>(k3.size(), 1), Geom());
+  }
   void states(std::vector<CState*>& v) override {
-    if (causal3d_) { v.push_back(&s1); v.push_back(&s2); }
+    if (c1.causal) { v.push_back(&c1.st); v.push_back(&c2.st); }
   }
   NormRef first_norm(Ctx&) const override { return n1.ref(true); }
-  Act run(Ctx& c, const Act& x, NormRef next) override {
-    Model* m = c.m;
-    Geom g3 = causal3d_ ? causal3d(3, 3, 3) : causal3d(1, 3, 3);
-    const Geom g1 = Geom();
-    if (causal3d_ && m->noncausal()) g3 = centred(g3, 1);           // ResnetNoncausalBlock: Conv3d padding 1
-    const Tens h = n1.apply(c, x, true, cin);
-    ConvOpts o1;
-    o1.ln = NormRef{&n2, true};
-    o1.keep_y = false;             // conv1's result is only ever seen through norm2 + SiLU
-    o1.tmode = m->tpad();
-    const int taps = causal3d_ ? 27 : 9;
-    const Act h2 = conv_causal(c, s1, h, m->conv_w(c1.key + ".weight", h.ld, c.dry), taps * h.ld, m->f32(c1.key + ".bias", c.dry), g3, cout, o1);
-    Tens xs = x.y;
-    if (cin != cout) xs = conv(c, x.y, m->conv_w(sc.key + ".weight", x.y.ld, c.dry), x.y.ld, m->f32(sc.key + ".bias", c.dry), g1, cout, ConvOpts()).y;
-    ConvOpts o2 = emit(next, m->tpad());
-    o2.res = &xs;
-    o2.res_mode = VT_RES_ADD;
-    return conv_causal(c, s2, h2.n, m->conv_w(c2.key + ".weight", h2.n.ld, c.dry), taps * h2.n.ld, m->f32(c2.key + ".bias", c.dry), g3, cout, o2);
-  }
+  Act run(Ctx& c, const Act& x, NormRef next) override { return residual_block(c, n1, n2, c1, c2, c1.cin != c1.cout ? &sc : nullptr, x, next); }
 };
 
 struct TBlock : Stage {            // ResnetCausalBlock1D, model_3dcausal.py:427-499
   int ch;
   Norm n1, n2;
-  ConvParams c1, c2;               // CausalConv1d: parameters at key + ".conv.weight"
-  CState s1, s2;                   // chunk state of the two convolutions: [B][2][H][W][C] each
-  void states(std::vector<CState*>& v) override { v.push_back(&s1); v.push_back(&s2); }
+  Site c1, c2;                     // CausalConv1d; chunk state of the two convolutions: [B][2][H][W][C] each
+  TBlock(Build& b, const std::string& key, int ch_) : ch(ch_) {
+    Geom g;
+    g.kt = 3; g.pt = 2;
+    if (b.m.noncausal()) g = centred(g, 1);            // ResnetBlock1D: Conv1d padding 1
+    // causal temporal blocks normalise single positions (model_3dcausal.py:476-487), the non-causal ones pixels over time (model_3dnoncausal.py:228-236)
+    b.norm(n1, key + ".norm1", ch, b.wrap() ? -1 : VT_GN_PIXEL);
+    b.norm(n2, key + ".norm2", ch, b.wrap() ? -1 : VT_GN_PIXEL);
+    c1.init(b, key + ".conv1", ch, ch, {3}, g, true);
+    c2.init(b, key + ".conv2", ch, ch, {3}, g, true);
+  }
+  void states(std::vector<CState*>& v) override { v.push_back(&c1.st); v.push_back(&c2.st); }
   // ResnetCausalBlock1D._fusable (vidtok_amd/modules.py): one launch for bf16, C = 128; in a tiled pass both convolutions must
   // stand at the same point of the chunk schedule and, past the first chunk, both caches must be there
   bool fusable(const Ctx& c) const {
     if (c.m->noncausal()) return false;                // the fused launch is the causal block
     if (!((c.m->dt == VT_BF16 || c.m->dt == VT_F16) && ch == 128 && n1.eps == n2.eps) || n1.group) return false;
     if (!c.m->tiled) return true;
-    if (s1.offset != s2.offset) return false;
-    return c.m->first_chunk || c.dry || (s1.frames >= 2 && s2.frames >= 2);
+    if (c1.st.offset != c2.st.offset) return false;
+    return c.m->first_chunk || c.dry || (c1.st.frames >= 2 && c2.st.frames >= 2);
   }
   NormRef first_norm(Ctx& c) const override { return fusable(c) ? NormRef() : n1.ref(true); }
   Act run(Ctx& c, const Act& x, NormRef next) override {
     Model* m = c.m;
     const Tens& xp = x.y;
-    Geom g;
-    g.kt = 3; g.pt = 2;
-    if (m->noncausal()) g = centred(g, 1);             // ResnetBlock1D: Conv1d padding 1
-    const std::string cv = m->cv();
     vt_tblock_desc d;
     memset(&d, 0, sizeof(d));
     d.dtype = xp.dt; d.C = ch; d.ld = xp.ld; d.B = xp.B; d.T = xp.T; d.HW = (int64_t)xp.H * xp.W; d.tmode = m->tpad();
@@ -680,24 +773,24 @@ struct TBlock : Stage {            // ResnetCausalBlock1D, model_3dcausal.py:427
     if (fus && m->tiled) {           // the launch keeps the chunk state itself: both caches rewritten in place
       const size_t cb = (size_t)xp.B * 2 * xp.H * xp.W * xp.ld * esize(xp.dt);
       d.tmode = m->first_chunk ? VT_TPAD_REPLICATE : VT_TPAD_CACHE;
-      d.cache1 = m->persistent(s1, cb, c.dry);
-      d.cache2 = m->persistent(s2, cb, c.dry);
+      d.cache1 = m->persistent(c1.st, cb, c.dry);
+      d.cache2 = m->persistent(c2.st, cb, c.dry);
       if (c.dry) d.cache1 = d.cache2 = (void*)16;
-      d.cache_offset = s1.offset;
+      d.cache_offset = c1.st.offset;
     }
     if (fus && vt_temporal_block_supported(&d)) {
-      if (m->tiled && !c.dry) s1.frames = s2.frames = 2;
+      if (m->tiled && !c.dry) c1.st.frames = c2.st.frames = 2;
       Act r;
       r.y = c.alloc(xp.B, xp.T, xp.H, xp.W, xp.ld, xp.dt, ch);
       const bool nx = next.norm != nullptr && next.norm->eps == n1.eps;
       if (nx) r.n = c.alloc(xp.B, xp.T, xp.H, xp.W, xp.ld, xp.dt, ch);
       d.x = xp.p; d.y = r.y.p; d.n_out = nx ? r.n.p : nullptr;
-      d.w1 = m->conv_w(c1.key + ".conv.weight", xp.ld, c.dry); d.b1 = m->f32(c1.key + ".conv.bias", c.dry);
-      d.w2 = m->conv_w(c2.key + ".conv.weight", xp.ld, c.dry); d.b2 = m->f32(c2.key + ".conv.bias", c.dry);
-      d.norm1_gamma = m->f32(n1.key + ".norm.weight", c.dry); d.norm1_beta = m->f32(n1.key + ".norm.bias", c.dry);
-      d.norm2_gamma = m->f32(n2.key + ".norm.weight", c.dry); d.norm2_beta = m->f32(n2.key + ".norm.bias", c.dry);
+      d.w1 = c1.w(c); d.b1 = c1.bias(c);
+      d.w2 = c2.w(c); d.b2 = c2.bias(c);
+      d.norm1_gamma = m->f32(n1.wkey(), c.dry); d.norm1_beta = m->f32(n1.bkey(), c.dry);         // (LayerNorm: fusable() refuses GroupNorm)
+      d.norm2_gamma = m->f32(n2.wkey(), c.dry); d.norm2_beta = m->f32(n2.bkey(), c.dry);
       if (nx) {
-        d.next_gamma = m->f32(next.norm->key + ".norm.weight", c.dry); d.next_beta = m->f32(next.norm->key + ".norm.bias", c.dry);
+        d.next_gamma = m->f32(next.norm->wkey(), c.dry); d.next_beta = m->f32(next.norm->bkey(), c.dry);
         d.ln_next_mode = next.silu ? 2 : 1;
         r.norm = next.norm; r.silu = next.silu;
       }
@@ -705,23 +798,21 @@ struct TBlock : Stage {            // ResnetCausalBlock1D, model_3dcausal.py:427
       if (!c.dry) M_CALL(vt_temporal_block(&d, c.stream));
       return r;
     }
-    const Tens h = n1.apply(c, x, true, ch);
-    ConvOpts o1;
-    o1.ln = NormRef{&n2, true};
-    o1.keep_y = false;
-    o1.tmode = m->tpad();
-    const Act h2 = conv_causal(c, s1, h, m->conv_w(c1.key + cv + ".weight", h.ld, c.dry), 3 * h.ld, m->f32(c1.key + cv + ".bias", c.dry), g, ch, o1);
-    ConvOpts o2 = emit(next, m->tpad());
-    o2.res = &xp;
-    o2.res_mode = VT_RES_ADD;
-    return conv_causal(c, s2, h2.n, m->conv_w(c2.key + cv + ".weight", h2.n.ld, c.dry), 3 * h2.n.ld, m->f32(c2.key + cv + ".bias", c.dry), g, ch, o2);
+    return residual_block(c, n1, n2, c1, c2, nullptr, x, next);
   }
 };
 
 struct Attn : Stage {              // AttnBlockWrapper, model_3dcausal.py:83-141 ("heads" = frames)
   int ch;
   Norm n;
-  std::string key;                 // q / k / v / proj_out: CausalConv3d 1x1x1 at key + ".q.conv.weight" ...
+  Site q_, k_, v_, proj;           // CausalConv3d 1x1x1; W_v is the row operand of a GEMM: plain rows
+  Attn(Build& b, const std::string& key, int ch_) : ch(ch_) {
+    b.norm(n, key + ".norm", ch, b.gn_site());
+    q_.init(b, key + ".q", ch, ch, {1, 1, 1}, Geom());
+    k_.init(b, key + ".k", ch, ch, {1, 1, 1}, Geom());
+    v_.init(b, key + ".v", ch, ch, {1, 1, 1}, Geom(), false, nullptr, 0, 0, true);
+    proj.init(b, key + ".proj_out", ch, ch, {1, 1, 1}, Geom());
+  }
   NormRef first_norm(Ctx&) const override { return n.ref(false); }
   Act run(Ctx& c, const Act& x, NormRef next) override {
     Model* m = c.m;
@@ -729,12 +820,10 @@ struct Attn : Stage {              // AttnBlockWrapper, model_3dcausal.py:83-141
     const Tens& xp = x.y;
     const int S = xp.H * xp.W, Z = xp.B * xp.T, Cc = xp.ld, Sp = pad8(S), dt = m->dt;
     M_CHECK(Cc == ch, "vt_model: attention over %d channels stored as %d (channel counts must be multiples of 8)", ch, Cc);
-    const Geom g1;
-    const std::string cv = m->cv();
-    const Tens q = conv(c, hn, m->conv_w(key + ".q" + cv + ".weight", Cc, c.dry), Cc, m->f32(key + ".q" + cv + ".bias", c.dry), g1, ch, ConvOpts()).y;
-    const Tens k = conv(c, hn, m->conv_w(key + ".k" + cv + ".weight", Cc, c.dry), Cc, m->f32(key + ".k" + cv + ".bias", c.dry), g1, ch, ConvOpts()).y;
-    const void* wv = m->conv_w(key + ".v" + cv + ".weight", Cc, c.dry, nullptr, 0, 0, true);
-    const float* bv = m->f32(key + ".v" + cv + ".bias", c.dry);
+    const Tens q = q_.run(c, hn, ConvOpts()).y;
+    const Tens k = k_.run(c, hn, ConvOpts()).y;
+    const void* wv = v_.w(c);
+    const float* bv = v_.bias(c);
     // V^T directly: the weight is the row operand; v's bias is added after P V (rows of P sum to 1)
     char* vT = gemm_nt(c, wv, false, hn.p, Z, Cc, S, Cc, dt, dt, Sp, nullptr);                // [Z][C][Sp]
     // scale = C^-0.5 as the Python host passes it: computed in double, rounded once to float
@@ -757,25 +846,31 @@ struct Attn : Stage {              // AttnBlockWrapper, model_3dcausal.py:83-141
     ConvOpts op = emit(next);
     op.res = &xp;
     op.res_mode = VT_RES_ADD;
-    return conv(c, o, m->conv_w(key + ".proj_out" + cv + ".weight", Cc, c.dry), Cc, m->f32(key + ".proj_out" + cv + ".bias", c.dry), g1, ch, op);
+    return proj.run(c, o, op);
   }
 };
 
 struct Down : Stage {              // Downsample: F.pad(0,1,0,1) + conv3x3 stride 2, model_3dcausal.py:215-230
-  int ch;
-  std::string key;                 // nn.Conv2d at key + ".conv.weight"
-  Act run(Ctx& c, const Act& x, NormRef next) override {
+  Site cv;                         // nn.Conv2d at key + ".conv"
+  Down(Build& b, const std::string& key, int ch) {
     Geom g;
     g.kh = 3; g.kw = 3; g.sh = 2; g.sw = 2; g.ph_hi = 1; g.pw_hi = 1;
-    return conv(c, x.y, c.m->conv_w(key + ".conv.weight", x.y.ld, c.dry), 9 * x.y.ld, c.m->f32(key + ".conv.bias", c.dry), g, ch, emit(next));
+    cv.init(b, key + ".conv", ch, ch, {3, 3}, g);
   }
+  Act run(Ctx& c, const Act& x, NormRef next) override { return cv.run(c, x.y, emit(next)); }
 };
 
 struct TimeDown : Stage {          // TimeDownsampleResCausal2x, model_3dcausal.py:233-252
-  int ch;
-  std::string key;                 // CausalConv3d at key + ".conv.conv.weight", key + ".mix_factor"
-  CState sc, sp;                   // the convolution's cache (one frame) and the pooling branch's (the chunk's last frame)
-  void states(std::vector<CState*>& v) override { v.push_back(&sc); v.push_back(&sp); }
+  std::string mix_key;             // key + ".mix_factor"
+  Site cv;                         // CausalConv3d at key + ".conv"; its cache holds one frame
+  CState sp;                       // the pooling branch's cache (the chunk's last frame)
+  TimeDown(Build& b, const std::string& key, int ch) : mix_key(key + ".mix_factor") {
+    Geom g = causal3d(3, 3, 3, 2, 1, 1);
+    if (b.m.noncausal()) g = centred(g, 0);                           // stride-2 Conv3d with padding (0,1,1) over [x, 0]
+    cv.init(b, key + ".conv", ch, ch, {3, 3, 3}, g, true);
+    b.sh[mix_key] = {1};
+  }
+  void states(std::vector<CState*>& v) override { v.push_back(&cv.st); v.push_back(&sp); }
   Act run(Ctx& c, const Act& x, NormRef next) override {
     Model* m = c.m;
     const Tens& xp = x.y;
@@ -790,37 +885,35 @@ struct TimeDown : Stage {          // TimeDownsampleResCausal2x, model_3dcausal.
       }
     }
     if (!c.dry) M_CALL(vt_time_avgpool3s2(xp.p, pc, x1.p, xp.dt, xp.B, xp.T, (int64_t)xp.H * xp.W, xp.ld, tm, c.stream));
-    if (m->tiled) {
-      const int64_t fr = (int64_t)xp.H * xp.W * xp.ld;
-      char* buf = m->persistent(sp, (size_t)xp.B * fr * esize(xp.dt), c.dry);
-      gather(c, xp.p, xp.T, buf, 1, 0, std::vector<int>{xp.T - 1}, xp.B, fr, (int)esize(xp.dt));
-      if (!c.dry) sp.frames = 1;
-    }
+    if (m->tiled) keep_frames(c, sp, xp, {xp.T - 1});
     ConvOpts o = emit(next, m->tpad());
     o.res = &x1;
     o.res_mode = VT_RES_MIX;
-    o.mix = m->f32(key + ".mix_factor", c.dry);
-    Geom g = causal3d(3, 3, 3, 2, 1, 1);
-    if (m->noncausal()) g = centred(g, 0);                            // stride-2 Conv3d with padding (0,1,1) over [x, 0]
-    const std::string ck = key + ".conv" + m->cv();
-    return conv_causal(c, sc, xp, m->conv_w(ck + ".weight", xp.ld, c.dry), 27 * xp.ld, m->f32(ck + ".bias", c.dry), g, ch, o);
+    o.mix = m->f32(mix_key, c.dry);
+    return cv.run(c, xp, o);
   }
 };
 
 struct Up : Stage {                // Upsample: nearest x2 + conv3x3 as four parity classes, model_3dcausal.py:200-212
   int ch;
-  std::string key;
+  Site par[2][2];                  // nn.Conv2d at key + ".conv", the 2x2 window of output rows / columns of parity py / px
+  Up(Build& b, const std::string& key, int ch_) : ch(ch_) {
+    for (int py = 0; py < 2; ++py)
+      for (int px = 0; px < 2; ++px) {
+        Geom g;
+        g.kh = 2; g.kw = 2; g.ph = 1 - py; g.pw = 1 - px; g.ph_hi = py; g.pw_hi = px;
+        par[py][px].init(b, key + ".conv", ch, ch, {3, 3}, g, false, xf_space_parity, py, px);
+      }
+  }
   Act run(Ctx& c, const Act& x, NormRef) override {
     const Tens& xp = x.y;
     Act r;
     r.y = c.alloc(xp.B, xp.T, 2 * xp.H, 2 * xp.W, pad8(ch), c.m->dt, ch);
     for (int py = 0; py < 2; ++py)
       for (int px = 0; px < 2; ++px) {
-        Geom g;
-        g.kh = 2; g.kw = 2; g.ph = 1 - py; g.pw = 1 - px; g.ph_hi = py; g.pw_hi = px;
         ConvOpts o;
         o.out = &r.y; o.ys = 1; o.ys_oh = py; o.ys_ow = px;
-        conv(c, xp, c.m->conv_w(key + ".conv.weight", xp.ld, c.dry, xf_space_parity, py, px), 4 * xp.ld, c.m->f32(key + ".conv.bias", c.dry), g, ch, o);
+        par[py][px].run(c, xp, o);
       }
     return r;
   }
@@ -829,56 +922,63 @@ struct Up : Stage {                // Upsample: nearest x2 + conv3x3 as four par
 struct TimeUp : Stage {            // TimeUpsampleResCausal2x: v1.0 nearest as two parity classes (model_3dcausal.py:255-273);
   int ch;                          // v1.1 nearest / trilinear up-sampling, then the 27-tap convolution (model_3dcausal_v1_1.py:305-343)
   int n_up = 1;                    // num_temp_upsample: 1, 2, 4 ... along the decoder (how many frames the trilinear head covers)
-  std::string key;
-  CState sc, su;                   // the convolution's cache (two frames) and the trilinear interpolation's (num_temp_upsample frames)
-  void states(std::vector<CState*>& v) override { v.push_back(&sc); v.push_back(&su); }
+  std::string mix_key;             // key + ".mix_factor"
+  // the sites of the one Conv3d at key + ".conv".  v1.1: the 27-tap convolution itself, whose cache holds two frames.  v1.0 and
+  // non-causal: the parity classes par[0 / 1] of the even / odd output frames over pre-summed taps; v1.0 also the three-product form,
+  // U = [W0, W2] over a frame pair and V = W1 per frame (no bias: U's launch adds it)
+  Site full, par[2], u3, v3;
+  CState su;                       // the trilinear interpolation's cache (num_temp_upsample frames)
+  TimeUp(Build& b, const std::string& key, int ch_, int n_up_) : ch(ch_), n_up(n_up_), mix_key(key + ".mix_factor") {
+    const std::vector<int64_t> k = {3, 3, 3};
+    b.sh[mix_key] = {1};
+    if (b.m.v11()) {
+      full.init(b, key + ".conv", ch, ch, k, causal3d(3, 3, 3), true);
+      return;
+    }
+    const bool nc = b.m.noncausal();
+    Geom g, gv;
+    g.kt = 2; g.kh = 3; g.kw = 3; g.pt = 1; g.ph = 1; g.pw = 1; g.ph_hi = 1; g.pw_hi = 1;
+    gv.kh = 3; gv.kw = 3; gv.ph = 1; gv.pw = 1; gv.ph_hi = 1; gv.pw_hi = 1;
+    // causal (window ends at the output frame):  o[2j] = (W0+W1) x[j-1] + W2 x[j],  o[2j+1] = W0 x[j-1] + (W1+W2) x[j]
+    // centred (TimeUpsampleRes2x, model_3dnoncausal.py:93-115):  o[2j] = W0 x[j-1] + (W1+W2) x[j],  o[2j+1] = (W0+W1) x[j] + W2 x[j+1]
+    for (int p = 0; p < 2; ++p) par[p].init(b, key + ".conv", ch, ch, k, nc ? centred(g, 1 - p) : g, false, xf_time_parity, nc ? p : 1 - p, 0);
+    if (nc) return;
+    u3.init(b, key + ".conv", ch, ch, k, g, false, xf_time_up3, 2, 0);
+    v3.init(b, key + ".conv", ch, ch, k, gv, false, xf_time_up3, 3, 0);
+  }
+  void states(std::vector<CState*>& v) override { v.push_back(&full.st); v.push_back(&su); }
   bool time_up() const override { return true; }
   // later chunks of a tiled pass with trilinear up-sampling: [cache | x] interpolated, the frames the previous chunk already
   // delivered left out (TimeUpsampleResCausal2x._interp_v11 of the Python host; model_3dcausal_v1_1.py:325-343)
   Tens interp_cached(Ctx& c, const Tens& xp) {
-    Model* m = c.m;
-    const int n = n_up, T = xp.T, es = (int)esize(xp.dt);
+    const int n = n_up, T = xp.T;
     const int64_t fr = (int64_t)xp.H * xp.W * xp.ld;
     const int nc = c.dry ? n : su.frames;
     M_CHECK(nc >= 1, "vt_model: time up-sampler cache missing (the first chunk must come first)");
     const int Tc = nc + T;
-    const char* head = c.dry ? nullptr : (const char*)su.buf->p;
+    const Tens head = frames_at(xp, c.dry ? nullptr : su.buf->p, nc);
     if (Tc - 2 * n >= nc) {
       Tens up = c.alloc(xp.B, 2 * Tc - 2 * n, xp.H, xp.W, xp.ld, xp.dt, xp.ld);
-      if (!c.dry) M_CALL(vt_time_lerp2x_cat(head, nc, xp.p, up.p, xp.dt, xp.B, T, 2 * n, fr, c.stream));
-      std::vector<int> keep;
-      for (int t = Tc - 2 * n - nc; t < Tc - n - nc; ++t) keep.push_back(t);
-      char* buf = m->persistent(su, (size_t)xp.B * keep.size() * fr * es, c.dry);
-      gather(c, xp.p, T, buf, (int)keep.size(), 0, keep, xp.B, fr, es);
-      if (!c.dry) su.frames = (int)keep.size();
+      if (!c.dry) M_CALL(vt_time_lerp2x_cat(head.p, nc, xp.p, up.p, xp.dt, xp.B, T, 2 * n, fr, c.stream));
+      keep_frames(c, su, xp, range(Tc - 2 * n - nc, Tc - n - nc));
       return up;
     }
     Tens xc = c.alloc(xp.B, Tc, xp.H, xp.W, xp.ld, xp.dt, xp.ld);     // [cache | x]
-    std::vector<int> all;
-    for (int t = 0; t < nc; ++t) all.push_back(t);
-    gather(c, head, nc, xc.p, Tc, 0, all, xp.B, fr, es);
-    all.clear();
-    for (int t = 0; t < T; ++t) all.push_back(t);
-    gather(c, xp.p, T, xc.p, Tc, nc, all, xp.B, fr, es);
-    std::vector<int> keep;
-    for (int t = std::max(0, Tc - 2 * n); t < Tc - n; ++t) keep.push_back(t);
-    char* buf = m->persistent(su, (size_t)xp.B * keep.size() * fr * es, c.dry);   // (xc is a copy: the cache buffer is free to be rewritten)
-    gather(c, xc.p, Tc, buf, (int)keep.size(), 0, keep, xp.B, fr, es);
-    if (!c.dry) su.frames = (int)keep.size();
-    Tens full = c.alloc(xp.B, 2 * Tc, xp.H, xp.W, xp.ld, xp.dt, xp.ld);
-    if (!c.dry) M_CALL(vt_time_lerp2x(xc.p, full.p, xp.dt, xp.B, Tc, fr, c.stream));
+    gather(c, head, xc.p, Tc, 0, range(0, nc));
+    gather(c, xp, xc.p, Tc, nc, range(0, T));
+    keep_frames(c, su, xc, range(std::max(0, Tc - 2 * n), Tc - n));    // (xc is a copy: the cache buffer is free to be rewritten)
+    Tens all = c.alloc(xp.B, 2 * Tc, xp.H, xp.W, xp.ld, xp.dt, xp.ld);
+    if (!c.dry) M_CALL(vt_time_lerp2x(xc.p, all.p, xp.dt, xp.B, Tc, fr, c.stream));
     Tens up = c.alloc(xp.B, 2 * Tc - 2 * n, xp.H, xp.W, xp.ld, xp.dt, xp.ld);
-    all.clear();
-    for (int t = 2 * n; t < 2 * Tc; ++t) all.push_back(t);
-    gather(c, full.p, 2 * Tc, up.p, 2 * Tc - 2 * n, 0, all, xp.B, fr, es);
+    gather(c, all, up.p, up.T, 0, range(2 * n, 2 * Tc));
     return up;
   }
   Act conv_of(Ctx& c, const Tens& up, NormRef next) {
     ConvOpts o = emit(next, VT_TPAD_REPLICATE);
     o.res = &up;
     o.res_mode = VT_RES_MIX;
-    o.mix = c.m->f32(key + ".mix_factor", c.dry);
-    return conv_causal(c, sc, up, c.m->conv_w(key + ".conv.conv.weight", up.ld, c.dry), 27 * up.ld, c.m->f32(key + ".conv.conv.bias", c.dry), causal3d(3, 3, 3), ch, o);
+    o.mix = c.m->f32(mix_key, c.dry);
+    return full.run(c, up, o);
   }
   Act run_v11(Ctx& c, const Act& x, NormRef next) {
     const Tens& xp = x.y;
@@ -887,35 +987,22 @@ struct TimeUp : Stage {            // TimeUpsampleResCausal2x: v1.0 nearest as t
     if (c.m->tiled && !c.m->first_chunk && c.m->cfg.interpolation_mode == 1) return conv_of(c, interp_cached(c, xp), next);
     Tens up = c.alloc(xp.B, 2 * T, xp.H, xp.W, xp.ld, xp.dt, xp.ld);
     if (c.m->cfg.interpolation_mode == 0) {                            // nearest: up[t] = x[t / 2]
-      for (int j0 = 0; j0 < 2 * T; j0 += 128) {
-        int32_t idx[128];
-        const int n = std::min(128, 2 * T - j0);
-        for (int j = 0; j < n; ++j) idx[j] = (j0 + j) / 2;
-        if (!c.dry) M_CALL(vt_gather_frames(xp.p, up.p + (size_t)j0 * fr * esize(xp.dt), (int)esize(xp.dt), xp.B, fr, (int64_t)T * fr, (int64_t)2 * T * fr, idx, n, c.stream));
-      }
+      std::vector<int> half = range(0, 2 * T);
+      for (int& t : half) t /= 2;
+      gather(c, xp, up.p, 2 * T, 0, half);
     } else {
       // trilinear, first chunk (the only one here): the first n_up frames are interpolated on their own, the rest likewise
       // (F.interpolate on x[:, :n] and x[:, n:] separately, model_3dcausal_v1_1.py:327-341); one launch per clip and part
       const int hn = std::min(n_up, T);
       auto lerp_part = [&](int t0, int n, int out_t0) {
         Tens part = c.alloc(xp.B, n, xp.H, xp.W, xp.ld, xp.dt, xp.ld);
-        for (int j0 = 0; j0 < n; j0 += 128) {
-          int32_t idx[128];
-          const int m = std::min(128, n - j0);
-          for (int j = 0; j < m; ++j) idx[j] = t0 + j0 + j;
-          if (!c.dry) M_CALL(vt_gather_frames(xp.p, part.p + (size_t)j0 * fr * esize(xp.dt), (int)esize(xp.dt), xp.B, fr, (int64_t)T * fr, (int64_t)n * fr, idx, m, c.stream));
-        }
+        gather(c, xp, part.p, n, 0, range(t0, t0 + n));
         for (int b = 0; b < xp.B; ++b)
           if (!c.dry)
             M_CALL(vt_time_lerp2x(part.p + (size_t)b * n * fr * esize(xp.dt), up.p + ((size_t)b * 2 * T + out_t0) * fr * esize(xp.dt), xp.dt, 1, n, fr, c.stream));
       };
-      if (c.m->tiled) {            // first chunk of a tiled pass: keep the last n_up frames for the next chunk's interpolation
-        std::vector<int> keep;
-        for (int t = std::max(0, T - n_up); t < T; ++t) keep.push_back(t);
-        char* buf = c.m->persistent(su, (size_t)xp.B * keep.size() * fr * esize(xp.dt), c.dry);
-        gather(c, xp.p, T, buf, (int)keep.size(), 0, keep, xp.B, fr, (int)esize(xp.dt));
-        if (!c.dry) su.frames = (int)keep.size();
-      }
+      // first chunk of a tiled pass: keep the last n_up frames for the next chunk's interpolation
+      if (c.m->tiled) keep_frames(c, su, xp, range(std::max(0, T - n_up), T));
       lerp_part(0, hn, 0);
       if (T > n_up) lerp_part(n_up, T - n_up, 2 * hn);
     }
@@ -929,26 +1016,20 @@ struct TimeUp : Stage {            // TimeUpsampleResCausal2x: v1.0 nearest as t
     // the consumer's LayerNorm from the two launches' epilogues where they can take it (TimeUpsampleResCausal2x.run of the Python host)
     bool emit_ln = next.norm != nullptr;
     Tens nbuf;
-    Geom g;
-    g.kt = 2; g.kh = 3; g.kw = 3; g.pt = 1; g.ph = 1; g.pw = 1; g.ph_hi = 1; g.pw_hi = 1;
-    const float* mf = c.m->f32(key + ".mix_factor", c.dry);
-    const bool nc = c.m->noncausal();
-    const std::string ck = key + ".conv" + c.m->cv();
-    if (!nc) {
+    const float* mf = c.m->f32(mix_key, c.dry);
+    if (!c.m->noncausal()) {
       // three frame products instead of four (vt_time_upsample3; time_parity_upsample of the Python host): U[j] = W0 x[j-1] + W2 x[j] is
       // shared by the two frames of a pair, V[j] = W1 x[j] by neighbouring pairs -- o[2j] = U[j] + V[j-1], o[2j+1] = U[j] + V[j].
       // Asked with the LayerNorm the launch would really carry, before anything is allocated or packed.
       ConvOpts o;
       Tens probe = r.y;
       probe.p = nullptr;
-      o.out = &r.y; o.yt_mul = 2; o.yt_off = 0; o.plan_only = true; o.tup3_probe = true;
+      o.out = &r.y; o.yt_mul = 2; o.yt_off = 0;
       if (emit_ln) { o.ln = next; o.ln_out = &probe; o.ln_optional = true; }
       o.res = &xp; o.res_mode = VT_RES_MIX; o.mix = mf;
-      const Act q = conv(c, xp, (const void*)16, 18 * xp.ld, nullptr, g, ch, o);
+      const Act q = u3.probe(c, xp, o, true);
       if (q.tup3) {
-        Geom gv;
-        gv.kh = 3; gv.kw = 3; gv.ph = 1; gv.pw = 1; gv.ph_hi = 1; gv.pw_hi = 1;
-        const Act v = conv(c, xp, c.m->conv_w(ck + ".weight", xp.ld, c.dry, xf_time_up3, 3, 0), 9 * xp.ld, nullptr, gv, ch, ConvOpts());
+        const Act v = v3.run(c, xp, ConvOpts(), false);
         ConvOpts u;
         u.out = &r.y; u.yt_mul = 2; u.yt_off = 0; u.tup3_v = &v.y;
         u.res = &xp; u.res_mode = VT_RES_MIX; u.mix = mf;
@@ -956,7 +1037,7 @@ struct TimeUp : Stage {            // TimeUpsampleResCausal2x: v1.0 nearest as t
           nbuf = c.alloc(xp.B, 2 * xp.T, xp.H, xp.W, pad8(ch), c.m->dt, ch);
           u.ln = next; u.ln_out = &nbuf;
         }
-        conv(c, xp, c.m->conv_w(ck + ".weight", xp.ld, c.dry, xf_time_up3, 2, 0), 18 * xp.ld, c.m->f32(ck + ".bias", c.dry), g, ch, u);
+        u3.run(c, xp, u);
         if (q.has_n()) { r.n = nbuf; r.norm = next.norm; r.silu = next.silu; }
         return r;
       }
@@ -967,25 +1048,17 @@ struct TimeUp : Stage {            // TimeUpsampleResCausal2x: v1.0 nearest as t
       ConvOpts o;
       Tens probe = r.y;
       probe.p = nullptr;
-      o.out = &r.y; o.yt_mul = 2; o.yt_off = 0; o.ln = next; o.ln_out = &probe; o.ln_optional = true; o.plan_only = true;
+      o.out = &r.y; o.yt_mul = 2; o.yt_off = 0; o.ln = next; o.ln_out = &probe; o.ln_optional = true;
       o.res = &xp; o.res_mode = VT_RES_MIX; o.mix = mf;
-      Geom gp = g;
-      if (nc) gp = centred(g, 1);
-      emit_ln = conv(c, xp, c.m->conv_w(ck + ".weight", xp.ld, c.dry, xf_time_parity, nc ? 0 : 1, 0), 18 * xp.ld, c.m->f32(ck + ".bias", c.dry), gp, ch, o).has_n();
+      emit_ln = par[0].probe(c, xp, o).has_n();
       if (emit_ln) nbuf = c.alloc(xp.B, 2 * xp.T, xp.H, xp.W, pad8(ch), c.m->dt, ch);
     }
-    for (int par = 0; par < 2; ++par) {
+    for (int p = 0; p < 2; ++p) {
       ConvOpts o;
-      o.out = &r.y; o.yt_mul = 2; o.yt_off = par;
+      o.out = &r.y; o.yt_mul = 2; o.yt_off = p;
       if (emit_ln) { o.ln = next; o.ln_out = &nbuf; o.ln_optional = true; }
       o.res = &xp; o.res_mode = VT_RES_MIX; o.mix = mf;
-      // causal (window ends at the output frame):  o[2j] = (W0+W1) x[j-1] + W2 x[j],  o[2j+1] = W0 x[j-1] + (W1+W2) x[j]
-      // centred (TimeUpsampleRes2x, model_3dnoncausal.py:93-115):  o[2j] = W0 x[j-1] + (W1+W2) x[j],  o[2j+1] = (W0+W1) x[j] + W2 x[j+1]
-      const int early = nc ? par : (par == 0 ? 1 : 0);
-      Geom gp = g;
-      if (nc) gp = centred(g, par == 0 ? 1 : 0);
-      const Act a = conv(c, xp, c.m->conv_w(ck + ".weight", xp.ld, c.dry, xf_time_parity, early, 0), 18 * xp.ld, c.m->f32(ck + ".bias", c.dry), gp, ch, o);
-      if (emit_ln && !a.has_n()) emit_ln = false;
+      if (!par[p].run(c, xp, o).has_n()) emit_ln = false;
     }
     if (emit_ln) { r.n = nbuf; r.norm = next.norm; r.silu = next.silu; }
     return r;
@@ -998,185 +1071,96 @@ bool in_list(const int32_t* v, int n, int x) {
   return false;
 }
 
-typedef std::map<std::string, std::vector<int64_t>> Shapes;     // reference state_dict key -> parameter shape
-void sh_conv(Shapes& sh, const std::string& key, int cout, int cin, std::vector<int64_t> k) {
-  std::vector<int64_t> w = {cout, cin};
-  w.insert(w.end(), k.begin(), k.end());
-  sh[key + ".weight"] = w;
-  sh[key + ".bias"] = {cout};
-}
-bool g_group_norm = false;         // set by the builders from vt_model_config.norm_type while a graph is being built (single-threaded: vt_create)
-void sh_norm(Shapes& sh, const std::string& key, int c) {
-  sh[key + (g_group_norm ? ".weight" : ".norm.weight")] = {c};
-  sh[key + (g_group_norm ? ".bias" : ".norm.bias")] = {c};
-}
-// a norm of the graph under `key`; `site` = the view its call site hands to GroupNorm (vidtok_amd/modules.py SITE_*)
-void set_norm(Norm& n, const std::string& key, int site) {
-  n.key = key;
-  n.group = g_group_norm;
-  n.site = site;
-}
-
 struct Graph {
   std::vector<std::unique_ptr<Stage>> stages;
-  std::string conv_in, conv_out;
+  Site conv_in, conv_out;          // causal, or Conv3d padding 1; two frames of chunk state each
   Norm norm_out;
-  int c_first = 0, c_last = 0;
-  CState st_in, st_out;            // chunk state of conv_in / conv_out (two frames each)
+  // the order sessions index their state by (vt_session::st) and set_offsets walks
   void states(std::vector<CState*>& v) {
-    v.push_back(&st_in);
+    v.push_back(&conv_in.st);
     for (auto& st : stages) st->states(v);
-    v.push_back(&st_out);
+    v.push_back(&conv_out.st);
   }
   // cache offsets of an overlapped decode (AutoencodingEngineV11._overlap_offsets, autoencoder_v1_1.py:307-320): 1 at latent
   // rate, doubling at each temporal up-sampler (the up-sampler itself already works at the doubled rate); 0 = no look-ahead
   void set_offsets(bool overlap) {
     int off = overlap ? 1 : 0;
-    st_in.offset = off;
+    conv_in.st.offset = off;
     for (auto& st : stages) {
       if (st->time_up()) off *= 2;
       std::vector<CState*> v;
       st->states(v);
       for (CState* s : v) s->offset = off;
     }
-    st_out.offset = off;
+    conv_out.st.offset = off;
   }
 };
 
-// `wrap`: the 3-D / 1-D convolutions sit under a Causal* wrapper (a ".conv" level in their keys); false for the non-causal family
-ResBlock* res_block(Shapes& sh, const std::string& key, int cin, int cout, bool causal, bool wrap = true, int site = VT_GN_FRAME) {
-  const std::string sfx0 = (causal && wrap) ? ".conv" : "";
-  const std::vector<int64_t> k3 = causal ? std::vector<int64_t>{3, 3, 3} : std::vector<int64_t>{3, 3};
-  const std::vector<int64_t> k1 = causal ? std::vector<int64_t>{1, 1, 1} : std::vector<int64_t>{1, 1};
-  sh_norm(sh, key + ".norm1", cin);
-  sh_norm(sh, key + ".norm2", cout);
-  sh_conv(sh, key + ".conv1" + sfx0, cout, cin, k3);
-  sh_conv(sh, key + ".conv2" + sfx0, cout, cout, k3);
-  if (cin != cout) sh_conv(sh, key + ".nin_shortcut" + sfx0, cout, cin, k1);
-  auto* b = new ResBlock();
-  b->causal3d_ = causal; b->cin = cin; b->cout = cout;
-  set_norm(b->n1, key + ".norm1", site); set_norm(b->n2, key + ".norm2", site);
-  const std::string sfx = sfx0;
-  b->c1.key = key + ".conv1" + sfx; b->c2.key = key + ".conv2" + sfx; b->sc.key = key + ".nin_shortcut" + sfx;
-  return b;
-}
-TBlock* t_block(Shapes& sh, const std::string& key, int ch, bool wrap = true) {
-  sh_norm(sh, key + ".norm1", ch);
-  sh_norm(sh, key + ".norm2", ch);
-  sh_conv(sh, key + ".conv1" + (wrap ? ".conv" : ""), ch, ch, {3});
-  sh_conv(sh, key + ".conv2" + (wrap ? ".conv" : ""), ch, ch, {3});
-  auto* b = new TBlock();
-  b->ch = ch;
-  // causal temporal blocks normalise single positions (model_3dcausal.py:476-487), the non-causal ones pixels over time (model_3dnoncausal.py:228-236)
-  set_norm(b->n1, key + ".norm1", wrap ? -1 : VT_GN_PIXEL); set_norm(b->n2, key + ".norm2", wrap ? -1 : VT_GN_PIXEL);
-  b->c1.key = key + ".conv1"; b->c2.key = key + ".conv2";
-  return b;
-}
-Attn* attn(Shapes& sh, const std::string& key, int ch, bool wrap = true) {
-  sh_norm(sh, key + ".norm", ch);
-  for (const char* n : {".q", ".k", ".v", ".proj_out"}) sh_conv(sh, key + n + (wrap ? ".conv" : ""), ch, ch, {1, 1, 1});
-  auto* a = new Attn();
-  a->ch = ch; a->key = key;
-  set_norm(a->n, key + ".norm", wrap ? VT_GN_FRAME : VT_GN_CLIP);
-  return a;
-}
-
-Graph build_encoder(const vt_model_config& cf, Shapes& sh) {
-  Graph g;
-  g_group_norm = cf.norm_type == 1;
+void build_encoder(Build& b, Graph& g) {
+  const vt_model_config& cf = b.cf();
   const int L = cf.num_resolutions;
-  const bool wrap = cf.version != 2;
-  const std::string cv = wrap ? ".conv" : "";
+  const Geom g333 = b.wrap() ? causal3d(3, 3, 3) : centred(causal3d(3, 3, 3), 1);
   int block_in = cf.ch;
   for (int i = 0; i < L; ++i) {
     block_in = cf.ch * (i == 0 ? 1 : cf.ch_mult[i - 1]);
     const int block_out = cf.ch * cf.ch_mult[i];
     const std::string d = "encoder.down." + std::to_string(i), dt = "encoder.down_temporal." + std::to_string(i);
-    for (int b = 0; b < cf.num_res_blocks; ++b) {
-      g.stages.emplace_back(res_block(sh, d + ".block." + std::to_string(b), block_in, block_out, false));
-      g.stages.emplace_back(t_block(sh, dt + ".block." + std::to_string(b), block_out, wrap));
+    for (int j = 0; j < cf.num_res_blocks; ++j) {
+      g.stages.emplace_back(new ResBlock(b, d + ".block." + std::to_string(j), block_in, block_out, false));
+      g.stages.emplace_back(new TBlock(b, dt + ".block." + std::to_string(j), block_out));
       block_in = block_out;
     }
     if (in_list(cf.spatial_ds, cf.n_spatial_ds, i)) {
-      auto* s = new Down();
-      s->ch = block_in; s->key = d + ".downsample";
-      sh_conv(sh, d + ".downsample.conv", block_in, block_in, {3, 3});
-      g.stages.emplace_back(s);
-      if (in_list(cf.tempo_ds, cf.n_tempo_ds, i)) {
-        auto* t = new TimeDown();
-        t->ch = block_in; t->key = dt + ".downsample";
-        sh_conv(sh, dt + ".downsample.conv" + cv, block_in, block_in, {3, 3, 3});
-        sh[dt + ".downsample.mix_factor"] = {1};
-        g.stages.emplace_back(t);
-      }
+      g.stages.emplace_back(new Down(b, d + ".downsample", block_in));
+      if (in_list(cf.tempo_ds, cf.n_tempo_ds, i)) g.stages.emplace_back(new TimeDown(b, dt + ".downsample", block_in));
     }
   }
-  g.stages.emplace_back(res_block(sh, "encoder.mid.block_1", block_in, block_in, true, wrap, wrap ? VT_GN_FRAME : VT_GN_CLIP));
-  g.stages.emplace_back(attn(sh, "encoder.mid.attn_1", block_in, wrap));
-  g.stages.emplace_back(res_block(sh, "encoder.mid.block_2", block_in, block_in, true, wrap, wrap ? VT_GN_FRAME : VT_GN_CLIP));
-  g.conv_in = "encoder.conv_in" + cv; g.conv_out = "encoder.conv_out" + cv;
-  set_norm(g.norm_out, "encoder.norm_out", wrap ? VT_GN_FRAME : VT_GN_CLIP);
-  g.c_first = cf.ch; g.c_last = block_in;
-  sh_conv(sh, g.conv_in, cf.ch, cf.in_channels, {3, 3, 3});
-  sh_conv(sh, g.conv_out, cf.double_z ? 2 * cf.z_channels : cf.z_channels, block_in, {3, 3, 3});
-  sh_norm(sh, g.norm_out.key, block_in);
-  return g;
+  g.stages.emplace_back(new ResBlock(b, "encoder.mid.block_1", block_in, block_in, true, b.gn_site()));
+  g.stages.emplace_back(new Attn(b, "encoder.mid.attn_1", block_in));
+  g.stages.emplace_back(new ResBlock(b, "encoder.mid.block_2", block_in, block_in, true, b.gn_site()));
+  g.conv_in.init(b, "encoder.conv_in", cf.ch, cf.in_channels, {3, 3, 3}, g333, true);
+  g.conv_out.init(b, "encoder.conv_out", cf.double_z ? 2 * cf.z_channels : cf.z_channels, block_in, {3, 3, 3}, g333, true);
+  b.norm(g.norm_out, "encoder.norm_out", block_in, b.gn_site());
 }
 
-Graph build_decoder(const vt_model_config& cf, Shapes& sh) {
-  Graph g;
-  g_group_norm = cf.norm_type == 1;
+void build_decoder(Build& b, Graph& g) {
+  const vt_model_config& cf = b.cf();
   const int L = cf.num_resolutions;
-  const bool wrap = cf.version != 2;
-  const std::string cv = wrap ? ".conv" : "";
+  const Geom g333 = b.wrap() ? causal3d(3, 3, 3) : centred(causal3d(3, 3, 3), 1);
   int block_in = cf.ch * cf.ch_mult[L - 1];
   int n_up = 1;
-  g.c_first = block_in;
-  g.stages.emplace_back(res_block(sh, "decoder.mid.block_1", block_in, block_in, true, wrap, wrap ? VT_GN_FRAME : VT_GN_CLIP));
-  g.stages.emplace_back(attn(sh, "decoder.mid.attn_1", block_in, wrap));
-  g.stages.emplace_back(res_block(sh, "decoder.mid.block_2", block_in, block_in, true, wrap, wrap ? VT_GN_FRAME : VT_GN_CLIP));
+  g.conv_in.init(b, "decoder.conv_in", block_in, cf.z_channels, {3, 3, 3}, g333, true);
+  g.stages.emplace_back(new ResBlock(b, "decoder.mid.block_1", block_in, block_in, true, b.gn_site()));
+  g.stages.emplace_back(new Attn(b, "decoder.mid.attn_1", block_in));
+  g.stages.emplace_back(new ResBlock(b, "decoder.mid.block_2", block_in, block_in, true, b.gn_site()));
   for (int i = L - 1; i >= 0; --i) {
     const int block_out = cf.ch * cf.ch_mult[i];
     const std::string u = "decoder.up." + std::to_string(i), ut = "decoder.up_temporal." + std::to_string(i);
-    for (int b = 0; b < cf.num_res_blocks + 1; ++b) {
-      g.stages.emplace_back(res_block(sh, u + ".block." + std::to_string(b), block_in, block_out, false));
-      g.stages.emplace_back(t_block(sh, ut + ".block." + std::to_string(b), block_out, wrap));
+    for (int j = 0; j < cf.num_res_blocks + 1; ++j) {
+      g.stages.emplace_back(new ResBlock(b, u + ".block." + std::to_string(j), block_in, block_out, false));
+      g.stages.emplace_back(new TBlock(b, ut + ".block." + std::to_string(j), block_out));
       block_in = block_out;
     }
     if (in_list(cf.spatial_us, cf.n_spatial_us, i)) {
-      auto* s = new Up();
-      s->ch = block_in; s->key = u + ".upsample";
-      sh_conv(sh, u + ".upsample.conv", block_in, block_in, {3, 3});
-      g.stages.emplace_back(s);
+      g.stages.emplace_back(new Up(b, u + ".upsample", block_in));
       if (in_list(cf.tempo_us, cf.n_tempo_us, i)) {
-        auto* t = new TimeUp();
-        t->ch = block_in; t->key = ut + ".upsample";
-        t->n_up = n_up;
+        g.stages.emplace_back(new TimeUp(b, ut + ".upsample", block_in, n_up));
         n_up *= 2;
-        sh_conv(sh, ut + ".upsample.conv" + cv, block_in, block_in, {3, 3, 3});
-        sh[ut + ".upsample.mix_factor"] = {1};
-        g.stages.emplace_back(t);
       }
     }
   }
-  g.conv_in = "decoder.conv_in" + cv; g.conv_out = "decoder.conv_out" + cv;
-  set_norm(g.norm_out, "decoder.norm_out", wrap ? VT_GN_FRAME : VT_GN_CLIP);
-  g.c_last = block_in;
-  sh_conv(sh, g.conv_in, g.c_first, cf.z_channels, {3, 3, 3});
-  sh_conv(sh, g.conv_out, cf.out_ch, block_in, {3, 3, 3});
-  sh_norm(sh, g.norm_out.key, block_in);
-  return g;
+  g.conv_out.init(b, "decoder.conv_out", cf.out_ch, block_in, {3, 3, 3}, g333, true);
+  b.norm(g.norm_out, "decoder.norm_out", block_in, b.gn_site());
 }
 
 // conv_in -> stages -> norm_out + SiLU -> conv_out (fp32 NCTHW); each stage is told which norm its consumer starts with
-void run_graph(Ctx& c, Graph& g, const Tens& x_in, int cout_final, float* out_ncthw, int t_trim) {
+void run_graph(Ctx& c, Graph& g, const Tens& x_in, float* out_ncthw, int t_trim) {
   Model* m = c.m;
   int which = 1;                   // x_in lives in arena 0
   c.cur = &m->arena[which];
   c.cur->reset();
   const NormRef first = g.stages[0]->first_norm(c);
-  const Geom g333 = m->noncausal() ? centred(causal3d(3, 3, 3), 1) : causal3d(3, 3, 3);       // conv_in / conv_out: causal, or Conv3d padding 1
-  Act h = conv_causal(c, g.st_in, x_in, m->conv_w(g.conv_in + ".weight", x_in.ld, c.dry), 27 * x_in.ld, m->f32(g.conv_in + ".bias", c.dry), g333, g.c_first, emit(first, m->tpad()));
+  Act h = g.conv_in.run(c, x_in, emit(first, m->tpad()));
   for (size_t i = 0; i < g.stages.size(); ++i) {
     which ^= 1;
     c.cur = &m->arena[which];
@@ -1187,12 +1171,12 @@ void run_graph(Ctx& c, Graph& g, const Tens& x_in, int cout_final, float* out_nc
   which ^= 1;
   c.cur = &m->arena[which];
   c.cur->reset();
-  const Tens hn = g.norm_out.apply(c, h, true, g.c_last);
+  const Tens hn = g.norm_out.apply(c, h, true, g.conv_out.cin);
   ConvOpts o;
   o.ncthw = out_ncthw ? out_ncthw : (float*)16;      // dry runs pass no buffer
   o.t_trim = t_trim;
   o.tmode = m->tpad();
-  conv_causal(c, g.st_out, hn, m->conv_w(g.conv_out + ".weight", hn.ld, c.dry), 27 * hn.ld, m->f32(g.conv_out + ".bias", c.dry), g333, cout_final, o);
+  g.conv_out.run(c, hn, o);
 }
 
 int front_pad(const vt_model_config& cf, int T) {      // EncoderCausal3DPadding.forward: v1.0 pads f - 1 frames, v1.1 up to a multiple of f
@@ -1207,8 +1191,7 @@ void encode_impl(Model* m, Graph& g, const float* x, int B, int T, int H, int W,
   const int npad = front_pad(m->cfg, T);
   Tens xin = c.alloc(B, T + npad, H, W, pad8(m->cfg.in_channels), m->dt, pad8(m->cfg.in_channels));   // the kernel zero-fills the pad channels itself
   if (!dry) M_CALL(vt_ncthw_to_ndhwc(x, xin.p, m->dt, B, m->cfg.in_channels, T, H, W, xin.ld, npad, stream));
-  const int cout = m->cfg.double_z ? 2 * m->cfg.z_channels : m->cfg.z_channels;
-  run_graph(c, g, xin, cout, h_out, 0);
+  run_graph(c, g, xin, h_out, 0);
 }
 
 void decode_impl(Model* m, Graph& g, const float* z, int B, int T, int H, int W, float* x_out, hipStream_t stream, bool dry) {
@@ -1216,7 +1199,7 @@ void decode_impl(Model* m, Graph& g, const float* z, int B, int T, int H, int W,
   m->arena[0].reset();
   Tens zin = c.alloc(B, T, H, W, pad8(m->cfg.z_channels), m->dt, pad8(m->cfg.z_channels));
   if (!dry) M_CALL(vt_ncthw_to_ndhwc(z, zin.p, m->dt, B, m->cfg.z_channels, T, H, W, zin.ld, 0, stream));
-  run_graph(c, g, zin, m->cfg.out_ch, x_out, m->cfg.version != 0 ? 0 : m->cfg.time_downsample_factor - 1);   // v1.1 keeps every frame (the caller drops the padding's), the non-causal decoder drops nothing
+  run_graph(c, g, zin, x_out, m->cfg.version != 0 ? 0 : m->cfg.time_downsample_factor - 1);   // v1.1 keeps every frame (the caller drops the padding's), the non-causal decoder drops nothing
 }
 
 // ---- temporal tiling of the v1.1 tokenizers (AutoencodingEngineV11.tile_encode / tile_decode, autoencoder_v1_1.py:218-331) -----------
@@ -1349,7 +1332,7 @@ struct vt_model {
 };
 
 extern "C" int vt_create(const vt_model_config* cfg, int32_t compute_dtype, vt_model** out) {
-  try {
+  return guarded("vt_create", [&]() -> int {
     M_CHECK(cfg != nullptr && out != nullptr, "vt_create: null argument");
     M_CHECK(compute_dtype == VT_BF16 || compute_dtype == VT_F16 || compute_dtype == VT_F32 || compute_dtype == VT_BF16X3,
             "vt_create: compute dtype must be VT_BF16, VT_F16, VT_F32 or VT_BF16X3");
@@ -1372,8 +1355,9 @@ extern "C" int vt_create(const vt_model_config* cfg, int32_t compute_dtype, vt_m
     h->m.cfg = *cfg;
     h->m.x3 = compute_dtype == VT_BF16X3;              // fp32 storage, split-bf16 convolutions (set_compute_dtype("bf16x3") of the Python host)
     h->m.dt = h->m.x3 ? VT_F32 : compute_dtype;
-    h->enc = build_encoder(*cfg, h->shapes);
-    h->dec = build_decoder(*cfg, h->shapes);
+    Build b{h->m, h->shapes};
+    build_encoder(b, h->enc);
+    build_decoder(b, h->dec);
     h->enc.states(h->m.states);
     h->dec.states(h->m.states);
     if (h->m.fsq_proj()) {         // nn.Linear(dim, effective_codebook_dim) / back (regularizers.py:137-139)
@@ -1386,12 +1370,7 @@ extern "C" int vt_create(const vt_model_config* cfg, int32_t compute_dtype, vt_m
     for (const auto& kv : h->shapes) h->names.push_back(kv.first);
     *out = h;
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_create: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 extern "C" int vt_model_config_size(void) { return (int)sizeof(vt_model_config); }
@@ -1402,7 +1381,7 @@ extern "C" int vt_destroy(vt_model* h) {
 }
 
 extern "C" int vt_load_weight(vt_model* h, const char* ref_key, const float* data_host, const int64_t* shape, int32_t ndim) {
-  try {
+  return guarded("vt_load_weight", [&]() -> int {
     M_CHECK(h && ref_key && data_host && shape && ndim >= 1 && ndim <= 5, "vt_load_weight: bad argument");
     const auto want = h->shapes.find(ref_key);
     M_CHECK(want != h->shapes.end(), "vt_load_weight: '%s' is not a parameter of this model (vt_weight_name lists them)", ref_key);
@@ -1435,12 +1414,7 @@ extern "C" int vt_load_weight(vt_model* h, const char* ref_key, const float* dat
       }
     }
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_load_weight: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 namespace {
@@ -1464,7 +1438,7 @@ extern "C" int vt_latent_dims(const vt_model* h, int32_t T, int32_t H, int32_t W
 }
 
 extern "C" int64_t vt_workspace_bytes(vt_model* h, int32_t B, int32_t T, int32_t H, int32_t W) {
-  try {
+  return guarded("vt_workspace_bytes", [&]() -> int64_t {
     M_CHECK(h && B > 0 && T > 0 && H > 0 && W > 0, "vt_workspace_bytes: bad argument");
     Model& m = h->m;
     ArenaScope arenas(&m);
@@ -1475,50 +1449,34 @@ extern "C" int64_t vt_workspace_bytes(vt_model* h, int32_t B, int32_t T, int32_t
     decode_impl(&m, h->dec, nullptr, B, ld[1], ld[2], ld[3], nullptr, nullptr, true);
     const size_t peak = std::max(m.arena[0].peak, m.arena[1].peak);
     return (int64_t)(2 * ((peak + 255) & ~(size_t)255) + 512);
-  } catch (const Fail& f) {
-    return -1;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_workspace_bytes: %s", e.what());
-    return -1;
-  }
+  });
 }
 
 // Pack and upload every weight now (host-side repacking + blocking copies), so that the first vt_encode / vt_decode is as
 // asynchronous as the later ones -- e.g. before capturing a stream.  Walks both graphs dry on a minimal clip.
 extern "C" int vt_prepare(vt_model* h) {
-  try {
+  return guarded("vt_prepare", [&]() -> int {
     M_CHECK(h != nullptr, "vt_prepare: null handle");
     check_loaded_all(h);
     Model& m = h->m;
-    Arena save[2] = {m.arena[0], m.arena[1]};
-    m.arena[0] = Arena();
-    m.arena[1] = Arena();
-    m.prepare = true;
     const int s = 1 << m.cfg.n_spatial_ds, T = m.cfg.time_downsample_factor;
     int32_t ld[4];
     vt_latent_dims(h, T, 8 * s, 8 * s, ld);
-    try {
+    {
+      struct PrepareScope {        // Model::prepare for the length of the walk, off again on every exit path
+        Model& m;
+        explicit PrepareScope(Model& m_) : m(m_) { m.prepare = true; }
+        ~PrepareScope() { m.prepare = false; }
+      } preparing(m);
+      ArenaScope arenas(&m);
       encode_impl(&m, h->enc, nullptr, 1, T, 8 * s, 8 * s, nullptr, nullptr, true);
       decode_impl(&m, h->dec, nullptr, 1, ld[1], ld[2], ld[3], nullptr, nullptr, true);
-    } catch (...) {
-      m.prepare = false;
-      m.arena[0] = save[0];
-      m.arena[1] = save[1];
-      throw;
     }
-    m.prepare = false;
-    m.arena[0] = save[0];
-    m.arena[1] = save[1];
     if (m.fsq_proj())              // FSQ projections: uploaded with the rest
       for (const char* k : {"regularization.project_in.weight", "regularization.project_in.bias", "regularization.project_out.weight", "regularization.project_out.bias"})
         (void)m.f32(k, false);
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_prepare: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 // the reference state_dict keys of the model's parameters (sorted) with their shapes: a loader walks them
@@ -1566,7 +1524,7 @@ size_t tile_staging_bytes(const vt_model_config& cf, int B, int H, int W, int t_
 
 extern "C" int vt_encode(vt_model* h, const float* x, int32_t B, int32_t T, int32_t H, int32_t W, float* h_out, void* workspace,
                          int64_t workspace_bytes, vt_stream stream) {
-  try {
+  return guarded("vt_encode", [&]() -> int {
     M_CHECK(h && x && h_out && B > 0 && T > 0 && H > 0 && W > 0, "vt_encode: bad argument");
     const int ds = 1 << h->m.cfg.n_spatial_ds;
     M_CHECK(H % ds == 0 && W % ds == 0, "vt_encode: H and W must be multiples of %d", ds);
@@ -1576,29 +1534,19 @@ extern "C" int vt_encode(vt_model* h, const float* x, int32_t B, int32_t T, int3
     bind_workspace(h->m, workspace, workspace_bytes);
     encode_impl(&h->m, h->enc, x, B, T, H, W, h_out, reinterpret_cast<hipStream_t>(stream), false);
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_encode: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 extern "C" int vt_decode(vt_model* h, const float* z, int32_t B, int32_t Tz, int32_t Hz, int32_t Wz, float* x_out, void* workspace,
                          int64_t workspace_bytes, vt_stream stream) {
-  try {
+  return guarded("vt_decode", [&]() -> int {
     M_CHECK(h && z && x_out && B > 0 && Tz > 0 && Hz > 0 && Wz > 0, "vt_decode: bad argument");
     M_CHECK(h->m.cfg.version != 0 || (Tz << h->m.cfg.n_tempo_us) > h->m.cfg.time_downsample_factor - 1, "vt_decode: too few latent frames");
     check_loaded(h, "decoder.");
     bind_workspace(h->m, workspace, workspace_bytes);
     decode_impl(&h->m, h->dec, z, B, Tz, Hz, Wz, x_out, reinterpret_cast<hipStream_t>(stream), false);
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_decode: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 extern "C" int vt_regularize_kl(vt_model* h, const float* moments, const float* noise, float* z, float* kl_out, int32_t B, int32_t Tz,
@@ -1618,7 +1566,7 @@ extern "C" int vt_regularize_fsq(vt_model* h, const float* pre, float* z, int32_
     vt_set_error("vt_regularize_fsq: the handle's regularizer is not FSQ");
     return VT_ERR_ARG;
   }
-  try {
+  return guarded("vt_regularize_fsq", [&]() -> int {
     Model& m = h->m;
     const int64_t S = (int64_t)Tz * Hz * Wz;
     const int ncb = m.fsq_ncb();
@@ -1630,12 +1578,7 @@ extern "C" int vt_regularize_fsq(vt_model* h, const float* pre, float* z, int32_
     M_CALL(vt_fsq_quantize_cb(hp, codes, indices, m.cfg.levels, m.cfg.n_levels, B, ncb, S, stream));
     M_CALL(vt_channel_linear(codes, m.f32("regularization.project_out.weight", false), m.f32("regularization.project_out.bias", false), z, B, eff, dim, S, stream));
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_regularize_fsq: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 // FSQ: token indices -> latent codes (AutoencodingEngine.indices_to_latent / decode(..., decode_from_indices=True),
@@ -1645,7 +1588,7 @@ extern "C" int vt_indices_to_latent(vt_model* h, const int32_t* indices, float* 
     vt_set_error("vt_indices_to_latent: the handle's regularizer is not FSQ");
     return VT_ERR_ARG;
   }
-  try {
+  return guarded("vt_indices_to_latent", [&]() -> int {
     Model& m = h->m;
     const int64_t S = (int64_t)Tz * Hz * Wz;
     const int ncb = m.fsq_ncb();
@@ -1655,12 +1598,7 @@ extern "C" int vt_indices_to_latent(vt_model* h, const int32_t* indices, float* 
     M_CALL(vt_fsq_indices_to_codes_cb(indices, codes, m.cfg.levels, m.cfg.n_levels, B, ncb, S, stream));
     M_CALL(vt_channel_linear(codes, m.f32("regularization.project_out.weight", false), m.f32("regularization.project_out.bias", false), z, B, eff, dim, S, stream));
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_indices_to_latent: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 // forget the chunk state of a tiled pass (vt_tile_encode / vt_tile_decode do it themselves at the start of a clip) and give the
@@ -1691,7 +1629,7 @@ extern "C" int32_t vt_tile_latent_frames(const vt_model* h, int32_t T, int32_t t
 }
 
 extern "C" int64_t vt_tile_workspace_bytes(vt_model* h, int32_t B, int32_t T, int32_t H, int32_t W, int32_t t_chunk_enc, int32_t use_overlap) {
-  try {
+  return guarded("vt_tile_workspace_bytes", [&]() -> int64_t {
     M_CHECK(h && B > 0 && T > 0 && H > 0 && W > 0 && t_chunk_enc > 0, "vt_tile_workspace_bytes: bad argument");
     M_CHECK(h->m.v11(), "vt_tile_workspace_bytes: temporal tiling exists only in the v1.1 models (version 1)");
     Model& m = h->m;
@@ -1704,17 +1642,12 @@ extern "C" int64_t vt_tile_workspace_bytes(vt_model* h, int32_t B, int32_t T, in
     tile_decode_impl(&m, h->dec, nullptr, B, tz, Hz, Wz, t_chunk_enc / f, use_overlap != 0, nullptr, nullptr, nullptr, true);
     const size_t peak = std::max(m.arena[0].peak, m.arena[1].peak);
     return (int64_t)(tile_staging_bytes(m.cfg, B, H, W, t_chunk_enc) + 2 * ((peak + 255) & ~(size_t)255) + 1024);
-  } catch (const Fail& f) {
-    return -1;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_tile_workspace_bytes: %s", e.what());
-    return -1;
-  }
+  });
 }
 
 extern "C" int vt_tile_encode(vt_model* h, const float* x, int32_t B, int32_t T, int32_t H, int32_t W, int32_t t_chunk_enc, float* h_out,
                               void* workspace, int64_t workspace_bytes, vt_stream stream) {
-  try {
+  return guarded("vt_tile_encode", [&]() -> int {
     M_CHECK(h && x && h_out && B > 0 && T > 0 && H > 0 && W > 0, "vt_tile_encode: bad argument");
     M_CHECK(h->m.v11(), "vt_tile_encode: temporal tiling exists only in the v1.1 models (version 1)");
     M_CHECK(t_chunk_enc >= h->m.cfg.time_downsample_factor, "vt_tile_encode: t_chunk_enc must be at least the temporal factor");
@@ -1725,17 +1658,12 @@ extern "C" int vt_tile_encode(vt_model* h, const float* x, int32_t B, int32_t T,
     bind_workspace(h->m, workspace, workspace_bytes, skip);
     tile_encode_impl(&h->m, h->enc, x, B, T, H, W, t_chunk_enc, h_out, (char*)workspace, reinterpret_cast<hipStream_t>(stream), false);
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;                                  // TileScope has put the handle's tiled-pass state back
-  } catch (const std::exception& e) {
-    vt_set_error("vt_tile_encode: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 extern "C" int vt_tile_decode(vt_model* h, const float* z, int32_t B, int32_t Tz, int32_t Hz, int32_t Wz, int32_t t_chunk_dec, int32_t use_overlap,
                               float* x_out, void* workspace, int64_t workspace_bytes, vt_stream stream) {
-  try {
+  return guarded("vt_tile_decode", [&]() -> int {
     M_CHECK(h && z && x_out && B > 0 && Tz > 0 && Hz > 0 && Wz > 0 && t_chunk_dec > 0, "vt_tile_decode: bad argument");
     M_CHECK(h->m.v11(), "vt_tile_decode: temporal tiling exists only in the v1.1 models (version 1)");
     check_loaded(h, "decoder.");
@@ -1745,12 +1673,7 @@ extern "C" int vt_tile_decode(vt_model* h, const float* z, int32_t B, int32_t Tz
     bind_workspace(h->m, workspace, workspace_bytes, skip);
     tile_decode_impl(&h->m, h->dec, z, B, Tz, Hz, Wz, t_chunk_dec, use_overlap != 0, x_out, (char*)workspace, reinterpret_cast<hipStream_t>(stream), false);
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_tile_decode: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 // FSQ: the three statistics of the auxiliary loss on the pre-quantisation latent (FSQRegularizer.forward, regularizers.py:229-262):
@@ -1762,7 +1685,7 @@ extern "C" int vt_regularize_fsq_aux(vt_model* h, const float* pre, int32_t B, i
     vt_set_error("vt_regularize_fsq_aux: the handle's regularizer is not FSQ");
     return VT_ERR_ARG;
   }
-  try {
+  return guarded("vt_regularize_fsq_aux", [&]() -> int {
     Model& m = h->m;
     const int64_t S = (int64_t)Tz * Hz * Wz;
     // with the codebook axis kept the reference's own forward raises (its implicit codebook is one-dimensional, regularizers.py:143-146,234)
@@ -1775,12 +1698,7 @@ extern "C" int vt_regularize_fsq_aux(vt_model* h, const float* pre, int32_t B, i
       hq = hp;
     }
     return vt_fsq_aux_stats_avg(hq, m.cfg.levels, m.cfg.n_levels, B, S, inv_temperature, work, out3, nullptr, stream);
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_regularize_fsq_aux: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 // ---- sessions: the v1.1 tiling fed as the frames arrive (include/vidtok_amd.h, "Sessions") ----------------------------------------
@@ -1921,7 +1839,7 @@ int session_step(vt_session* s, const float* in, int n, float* out, int out_cap,
 }  // namespace
 
 extern "C" int vt_session_create(vt_model* h, int32_t kind, int32_t B, int32_t H, int32_t W, int32_t t_chunk, int32_t use_overlap, vt_session** out) {
-  try {
+  return guarded("vt_session_create", [&]() -> int {
     M_CHECK(out != nullptr, "vt_session_create: null argument");
     *out = nullptr;
     M_CHECK(h != nullptr, "vt_session_create: null handle");
@@ -1979,12 +1897,7 @@ extern "C" int vt_session_create(vt_model* h, int32_t kind, int32_t B, int32_t H
     M_HIP(hipMalloc(&s->pend.p, (size_t)B * s->cin * s->cap * H * W * sizeof(float)));
     *out = s.release();
     return VT_OK;
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_session_create: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 extern "C" int64_t vt_session_workspace_bytes(const vt_session* s) {
@@ -1997,28 +1910,18 @@ extern "C" int64_t vt_session_workspace_bytes(const vt_session* s) {
 
 extern "C" int vt_session_push(vt_session* s, const float* in, int32_t n, float* out, int32_t out_cap_frames, int32_t* n_out, void* workspace,
                                int64_t workspace_bytes, vt_stream stream) {
-  try {
+  return guarded("vt_session_push", [&]() -> int {
     M_CHECK(s != nullptr && in != nullptr && n >= 1, "vt_session_push: bad argument (a session, and n >= 1 frames)");
     return session_step(s, in, n, out, out_cap_frames, n_out, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, "vt_session_push");
-  } catch (const Fail& f) {
-    return f.code;                                  // SessionSwap / TileScope have put the handle's state back
-  } catch (const std::exception& e) {
-    vt_set_error("vt_session_push: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 extern "C" int vt_session_finish(vt_session* s, float* out, int32_t out_cap_frames, int32_t* n_out, void* workspace, int64_t workspace_bytes,
                                  vt_stream stream) {
-  try {
+  return guarded("vt_session_finish", [&]() -> int {
     return session_step(s, nullptr, 0, out, out_cap_frames, n_out, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), true,
                         "vt_session_finish");
-  } catch (const Fail& f) {
-    return f.code;
-  } catch (const std::exception& e) {
-    vt_set_error("vt_session_finish: %s", e.what());
-    return VT_ERR_ARG;
-  }
+  });
 }
 
 extern "C" int vt_session_destroy(vt_session* s) {

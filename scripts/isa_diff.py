@@ -55,8 +55,8 @@ def functions(text):
         if cur is None:
             continue
         ins = line.split("//")[0].strip()
-        if not ins:
-            continue
+        if not ins or ins == "...":                        # objdump's mark for the zero fill behind a code object's LAST function: which one
+            continue                                       # that is follows the order of instantiation in the host code, not the kernel
         ins = re.sub(r"<[^>]*>", "", ins).strip()          # branch target annotations (symbol + offset)
         out[cur].append(ins)
     for name, ins in out.items():                          # operands of the s_add/s_addc pair after s_getpc_b64: a symbol's distance

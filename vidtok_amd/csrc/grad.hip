@@ -9,9 +9,7 @@
 //
 // vt_layernorm_act_backward: per-row LayerNorm(+SiLU) backward over channels-last rows, mean / rstd recomputed from the
 // saved pre-norm rows; gamma / beta gradients as per-workgroup partials plus a fixed-order reduce.
-#include <algorithm>
-
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -220,8 +218,6 @@ int wgrad_plan(const vt_wgrad_desc* d, WgradPlan* p) {
   return VT_OK;
 }
 
-int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
-
 // ---- LayerNorm(+SiLU) backward -------------------------------------------------------------------------------------------
 constexpr int kLnBlock = 256;
 constexpr int kLnMaxJ = 8;         // channels per lane: C <= 512, every LayerNorm site of the models (instantiated for 1, 2, 4, 8)
@@ -327,10 +323,7 @@ __global__ __launch_bounds__(256) void partial_rows_reduce_kernel(const float* _
   if (dbeta != nullptr) dbeta[c] = sb;
 }
 
-int64_t ln_bwd_groups(int64_t M) {
-  const int64_t rows_per_wg = 4 * kLnRowsPerWave;
-  return std::max<int64_t>(1, std::min<int64_t>((M + rows_per_wg - 1) / rows_per_wg, 4096));
-}
+int64_t ln_bwd_groups(int64_t M) { return grid_for(M, 4 * kLnRowsPerWave, 4096); }
 
 }  // namespace
 
@@ -343,7 +336,7 @@ extern "C" int64_t vt_conv_wgrad_work_bytes(const vt_wgrad_desc* d) {
 }
 
 extern "C" int vt_conv_wgrad(const vt_wgrad_desc* d, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = as_stream(stream_);
   WgradPlan p;
   const int rc = wgrad_plan(d, &p);
   if (rc != VT_OK) return rc;
@@ -370,17 +363,12 @@ extern "C" int vt_conv_wgrad(const vt_wgrad_desc* d, vt_stream stream_) {
   a.KH = d->KH; a.KW = d->KW; a.st = d->st; a.sh = d->sh; a.sw = d->sw;
   a.pt = d->pt; a.ph = d->ph; a.pw = d->pw; a.tmode = d->tmode; a.ups_t = d->ups_t; a.ups_s = d->ups_s;
   const dim3 grid((unsigned)((p.K + kWgTile - 1) / kWgTile), (unsigned)((d->Cout + kWgTile - 1) / kWgTile), (unsigned)p.nsplit);
-  if (d->dtype == VT_BF16)
-    hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, dim3(kWgBlock), 0, stream, a);
-  else
-    hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(kWgBlock), 0, stream, a);
-  VT_CHECK_LAUNCH();
+  const int rc2 = vt_dispatch<float, bf16_t>(d->dtype, [&](auto t) { return launch(conv_wgrad_kernel<vt_t<decltype(t)>>, grid, dim3(kWgBlock), 0, stream, a); });
+  if (rc2 != VT_OK) return rc2;
   const int taps = d->KT * d->KH * d->KW;
   const int64_t n = (int64_t)d->Cout * d->Cin * taps + (d->db != nullptr ? d->Cout : 0);
-  hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a.part, a.bpart, d->dw, d->db,
-                     p.nsplit, d->Cout, d->Cin, taps, d->ldx, a.K);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(conv_wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a.part, a.bpart, d->dw, d->db,
+                p.nsplit, d->Cout, d->Cin, taps, d->ldx, a.K);
 }
 
 extern "C" int64_t vt_layernorm_act_backward_work_bytes(int64_t M, int32_t C) {
@@ -391,7 +379,7 @@ extern "C" int64_t vt_layernorm_act_backward_work_bytes(int64_t M, int32_t C) {
 extern "C" int vt_layernorm_act_backward(const void* y, const void* dn, int32_t dtype, int64_t ld, void* dx, int32_t dx_dtype, int64_t ldo,
                                          const float* gamma, const float* beta, float* dgamma, float* dbeta, int64_t M, int32_t C, float eps,
                                          int32_t silu, void* work, int64_t work_bytes, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = as_stream(stream_);
   VT_CHECK_ARG(y && dn && dx && gamma && beta && work, "vt_layernorm_act_backward: null pointer");
   VT_CHECK_ARG(M > 0 && C > 0 && C <= 64 * kLnMaxJ && ld >= C && ldo >= C && ldo <= 64 * ((C + 63) / 64),
                "vt_layernorm_act_backward: bad dims (M=%lld C=%d ld=%lld ldo=%lld; C <= 512, pad lanes of dx within the last 64)",
@@ -406,30 +394,14 @@ extern "C" int vt_layernorm_act_backward(const void* y, const void* dn, int32_t 
   float* bpart = reinterpret_cast<float*>(static_cast<char*>(work) + pbytes);
   const int64_t rows_per_wg = (M + groups - 1) / groups;
   const int nj = (C + 63) / 64;
-#define VT_LN_BWD_J(T, TO, J)                                                                                                              \
-  hipLaunchKernelGGL((layernorm_act_bwd_kernel<T, TO, J>), dim3((unsigned)groups), dim3(kLnBlock), 0, stream, static_cast<const T*>(y), \
-                     static_cast<const T*>(dn), ld, static_cast<TO*>(dx), ldo, gamma, beta, gpart, bpart, M, C, rows_per_wg, eps, silu)
-#define VT_LN_BWD(T, TO)          \
-  if (nj <= 1)                    \
-    VT_LN_BWD_J(T, TO, 1);        \
-  else if (nj <= 2)               \
-    VT_LN_BWD_J(T, TO, 2);        \
-  else if (nj <= 4)               \
-    VT_LN_BWD_J(T, TO, 4);        \
-  else                            \
-    VT_LN_BWD_J(T, TO, kLnMaxJ)
-  if (dtype == VT_F32) {
-    VT_LN_BWD(float, float);
-  } else if (dx_dtype == VT_F32) {
-    VT_LN_BWD(bf16_t, float);
-  } else {
-    VT_LN_BWD(bf16_t, bf16_t);
-  }
-#undef VT_LN_BWD_J
-#undef VT_LN_BWD
-  VT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(partial_rows_reduce_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, gpart, bpart, dgamma, dbeta,
-                     (int)groups, C);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const int rc = vt_dispatch_grad(dtype, dx_dtype, [&](auto t, auto to) {
+    using T = vt_t<decltype(t)>;
+    using TO = vt_t<decltype(to)>;
+    return vt_dispatch_int<1, 2, 4, kLnMaxJ>(nj <= 1 ? 1 : nj <= 2 ? 2 : nj <= 4 ? 4 : kLnMaxJ, [&](auto j) {
+      return launch(layernorm_act_bwd_kernel<T, TO, decltype(j)::value>, dim3((unsigned)groups), dim3(kLnBlock), 0, stream, static_cast<const T*>(y),
+                    static_cast<const T*>(dn), ld, static_cast<TO*>(dx), ldo, gamma, beta, gpart, bpart, M, C, rows_per_wg, eps, silu);
+    });
+  });
+  if (rc != VT_OK) return rc;
+  return launch(partial_rows_reduce_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, gpart, bpart, dgamma, dbeta, (int)groups, C);
 }

@@ -13,17 +13,11 @@
 // transpose (the attention GEMMs want K-contiguous operands), the alpha-mix of the time up-samplers forward and backward (with the
 // mix_factor gradient as fixed-order partials + a second launch), the adjoint of the x2 time interpolation, the cotangent's layout
 // change and a gradient add.  No float atomics anywhere: every result is bit-reproducible and every call is capture-safe.
-#include <algorithm>
-
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-
-inline unsigned grid_for(long long n, int per_block = kBlock, long long cap = 16384) {
-  return (unsigned)std::max<long long>(1, std::min<long long>((n + per_block - 1) / per_block, cap));
-}
 
 // ---- parity classes of the input, per axis -----------------------------------------------------------------------------------
 // input positions i = s j + r receive only the taps k0, k0 + s, ... (nk of them): as a stride-1 convolution over dy that is the flipped
@@ -313,8 +307,6 @@ __global__ __launch_bounds__(kBlock) void grad_add_kernel(const T* __restrict__ 
     o[i] = from_f32<T>(to_f32<T>(a[i]) + to_f32<T>(b[i]));
 }
 
-inline bool grad_dtype_ok(int dt) { return dt == VT_F32 || dt == VT_BF16; }
-
 // what vt_conv_dgrad launches: the classes of the virtual (up-sampled) rows and columns and where each class convolution writes
 struct DgradPlan {
   AxisClass ah[2], aw[2];
@@ -404,20 +396,17 @@ extern "C" int vt_dgrad_desc_size(void) { return (int)sizeof(vt_dgrad_desc); }
 
 extern "C" int vt_pack_conv_weight_dgrad(const float* w, void* out, int32_t out_dtype, int32_t Cout, int32_t Cin, int32_t cout_p, int32_t KT, int32_t KH,
                                          int32_t KW, int32_t sh, int32_t sw, int32_t ph, int32_t pw, int64_t ldw, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(w && out && Cout > 0 && Cin > 0 && cout_p >= Cout && KT > 0 && KH > 0 && KW > 0, "vt_pack_conv_weight_dgrad: bad arguments");
   VT_CHECK_ARG(grad_dtype_ok(out_dtype), "vt_pack_conv_weight_dgrad: out_dtype %d (fp32 or bf16)", out_dtype);
   VT_CHECK_ARG((sh == 1 || sh == 2) && (sw == 1 || sw == 2) && ph >= 0 && ph < KH && pw >= 0 && pw < KW, "vt_pack_conv_weight_dgrad: strides (%d, %d) in {1, 2}, pads (%d, %d) below the taps",
                sh, sw, ph, pw);
   VT_CHECK_ARG(sh + sw == 2 || (KT <= 4 && KH <= 4 && KW <= 4), "vt_pack_conv_weight_dgrad: taps (%d, %d, %d): 1 .. 4 an axis under a stride", KT, KH, KW);
   VT_CHECK_ARG(ldw >= (int64_t)KT * ((KH + sh - 1) / sh) * ((KW + sw - 1) / sw) * cout_p, "vt_pack_conv_weight_dgrad: ldw %lld", (long long)ldw);
-  const unsigned grid = grid_for((long long)sh * sw * Cin * ldw, kBlock, 8192);
-  if (out_dtype == VT_F32)
-    hipLaunchKernelGGL(pack_dgrad_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, w, static_cast<float*>(out), Cout, Cin, cout_p, KT, KH, KW, sh, sw, ph, pw, (long long)ldw);
-  else
-    hipLaunchKernelGGL(pack_dgrad_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, w, static_cast<bf16_t*>(out), Cout, Cin, cout_p, KT, KH, KW, sh, sw, ph, pw, (long long)ldw);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch<float, bf16_t>(out_dtype, [&](auto t) {
+    using TO = vt_t<decltype(t)>;
+    return launch(pack_dgrad_kernel<TO>, dim3(grid_for((long long)sh * sw * Cin * ldw, kBlock, 8192)), dim3(kBlock), 0, as_stream(stream_), w, static_cast<TO*>(out), Cout, Cin,
+                  cout_p, KT, KH, KW, sh, sw, ph, pw, (long long)ldw);
+  });
 }
 
 extern "C" int64_t vt_conv_dgrad_work_bytes(const vt_dgrad_desc* d) {
@@ -427,22 +416,18 @@ extern "C" int64_t vt_conv_dgrad_work_bytes(const vt_dgrad_desc* d) {
 
 extern "C" int vt_grad_fold(const void* src, int32_t src_dtype, const void* acc, void* dx, int32_t dx_dtype, int32_t B, int32_t T, int32_t H, int32_t W, int32_t C, int32_t lds,
                             int32_t lda, int32_t ldo, int32_t rep, int32_t ups_t, int32_t ups_s, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(src && dx && B > 0 && T > 0 && H > 0 && W > 0 && C > 0 && lds >= C && ldo >= C && ldo % 4 == 0 && (acc == nullptr || lda >= C),
                "vt_grad_fold: bad arguments");
   VT_CHECK_ARG(grad_dtype_ok(dx_dtype) && (src_dtype == VT_F32 || src_dtype == dx_dtype) && rep >= 0 && (ups_t | ups_s | 1) == 1,
                "vt_grad_fold: src_dtype %d (fp32 or dx's), dx_dtype %d, rep %d, ups (%d, %d)", src_dtype, dx_dtype, rep, ups_t, ups_s);
   FoldArgs a{src, acc, dx, B, T, H, W, C, lds, lda, ldo, rep, ups_t, ups_s};
-  const unsigned grid = grid_for((long long)B * T * H * W * (ldo / 4));
-  if (dx_dtype == VT_F32) hipLaunchKernelGGL((grad_fold_kernel<float, float>), dim3(grid), dim3(kBlock), 0, stream, a);
-  else if (src_dtype == VT_F32) hipLaunchKernelGGL((grad_fold_kernel<float, bf16_t>), dim3(grid), dim3(kBlock), 0, stream, a);
-  else hipLaunchKernelGGL((grad_fold_kernel<bf16_t, bf16_t>), dim3(grid), dim3(kBlock), 0, stream, a);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch_grad(dx_dtype, src_dtype, [&](auto to, auto ts) {
+    return launch(grad_fold_kernel<vt_t<decltype(ts)>, vt_t<decltype(to)>>, dim3(grid_for((long long)B * T * H * W * (ldo / 4), kBlock, 16384)), dim3(kBlock), 0,
+                  as_stream(stream_), a);
+  });
 }
 
 extern "C" int vt_conv_dgrad(const vt_dgrad_desc* d, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   DgradPlan p;
   const int rc = dgrad_prepare(d, &p);
   if (rc != VT_OK) return rc;
@@ -469,52 +454,38 @@ extern "C" int vt_conv_dgrad(const vt_dgrad_desc* d, vt_stream stream_) {
   f.acc = d->acc;
   f.dx = d->dx;
   f.B = d->B; f.T = d->Ti; f.H = d->Hi; f.W = d->Wi; f.C = d->Cin; f.ld = d->lddx; f.lda = d->ldacc; f.sh = d->sh; f.sw = d->sw;
-  const unsigned grid = grid_for((long long)d->B * d->Ti * d->Hi * d->Wi * (d->lddx / 4));
-  if (d->dx_dtype == VT_F32)
-    hipLaunchKernelGGL(strided_finish_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, f);
-  else
-    hipLaunchKernelGGL(strided_finish_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, f);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch<float, bf16_t>(d->dx_dtype, [&](auto t) {
+    return launch(strided_finish_kernel<vt_t<decltype(t)>>, dim3(grid_for((long long)d->B * d->Ti * d->Hi * d->Wi * (d->lddx / 4), kBlock, 16384)), dim3(kBlock), 0,
+                  as_stream(stream_), f);
+  });
 }
 
 extern "C" int vt_softmax_rows_backward(const void* p, int64_t ldp, const float* dp, void* ds, int64_t ldo, int32_t dtype, int64_t rows, int32_t cols, float scale,
                                         vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(p && dp && ds && rows > 0 && cols > 0 && ldp >= cols && ldo >= cols && grad_dtype_ok(dtype), "vt_softmax_rows_backward: bad arguments");
-  const unsigned grid = grid_for(rows, kBlock / 64, 8192);
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(softmax_rows_backward_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, static_cast<const float*>(p), (long long)ldp, dp, static_cast<float*>(ds),
-                       (long long)ldo, (long long)rows, cols, scale);
-  else
-    hipLaunchKernelGGL(softmax_rows_backward_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, static_cast<const bf16_t*>(p), (long long)ldp, dp, static_cast<bf16_t*>(ds),
-                       (long long)ldo, (long long)rows, cols, scale);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch<float, bf16_t>(dtype, [&](auto t) {
+    using T = vt_t<decltype(t)>;
+    return launch(softmax_rows_backward_kernel<T>, dim3(grid_for(rows, kBlock / 64, 8192)), dim3(kBlock), 0, as_stream(stream_), static_cast<const T*>(p), (long long)ldp, dp,
+                  static_cast<T*>(ds), (long long)ldo, (long long)rows, cols, scale);
+  });
 }
 
 extern "C" int vt_transpose_batched(const void* in, void* out, int32_t dtype, int32_t Z, int32_t R, int32_t C, int64_t ldi, int64_t ldo, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(in && out && Z > 0 && Z < 65536 && R > 0 && C > 0 && ldi >= C && ldo >= R && grad_dtype_ok(dtype), "vt_transpose_batched: bad arguments");
   const dim3 grid((unsigned)((ldo + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)Z);
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(transpose_kernel<uint32_t>, grid, dim3(kBlock), 0, stream, static_cast<const uint32_t*>(in), static_cast<uint32_t*>(out), R, C, (long long)ldi, (long long)ldo);
-  else
-    hipLaunchKernelGGL(transpose_kernel<uint16_t>, grid, dim3(kBlock), 0, stream, static_cast<const uint16_t*>(in), static_cast<uint16_t*>(out), R, C, (long long)ldi, (long long)ldo);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch_size<uint32_t, uint16_t>(dtype == VT_F32 ? 4 : 2, [&](auto t) {
+    using E = vt_t<decltype(t)>;
+    return launch(transpose_kernel<E>, grid, dim3(kBlock), 0, as_stream(stream_), static_cast<const E*>(in), static_cast<E*>(out), R, C, (long long)ldi, (long long)ldo);
+  });
 }
 
 extern "C" int vt_upsample_mix(const void* u, const void* c, const float* mix_factor, void* y, int32_t dtype, int64_t M, int32_t C, int32_t ld, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(u && c && mix_factor && y && M > 0 && C > 0 && ld >= C && grad_dtype_ok(dtype), "vt_upsample_mix: bad arguments");
-  const unsigned grid = grid_for(M * ld);
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(mix_forward_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, static_cast<const float*>(u), static_cast<const float*>(c), mix_factor, static_cast<float*>(y), (long long)M, C, ld);
-  else
-    hipLaunchKernelGGL(mix_forward_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, static_cast<const bf16_t*>(u), static_cast<const bf16_t*>(c), mix_factor, static_cast<bf16_t*>(y), (long long)M, C, ld);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch<float, bf16_t>(dtype, [&](auto t) {
+    using T = vt_t<decltype(t)>;
+    return launch(mix_forward_kernel<T>, dim3(grid_for(M * ld, kBlock, 16384)), dim3(kBlock), 0, as_stream(stream_), static_cast<const T*>(u), static_cast<const T*>(c), mix_factor,
+                  static_cast<T*>(y), (long long)M, C, ld);
+  });
 }
 
 extern "C" int64_t vt_upsample_mix_backward_work_bytes(int64_t M, int32_t ld) {
@@ -524,52 +495,44 @@ extern "C" int64_t vt_upsample_mix_backward_work_bytes(int64_t M, int32_t ld) {
 
 extern "C" int vt_upsample_mix_backward(const void* dy, const void* u, const void* c, const float* mix_factor, void* du, void* dc, float* dmix, int32_t dtype, int64_t M,
                                         int32_t C, int32_t ld, void* work, int64_t work_bytes, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = as_stream(stream_);
   VT_CHECK_ARG(dy && u && c && mix_factor && du && dc && dmix && M > 0 && C > 0 && ld >= C && grad_dtype_ok(dtype), "vt_upsample_mix_backward: bad arguments");
   const int blocks = mix_blocks(M * ld);
   VT_CHECK_ARG(work != nullptr && work_bytes >= (int64_t)blocks * 4, "vt_upsample_mix_backward: workspace of %d bytes needed", blocks * 4);
   float* part = static_cast<float*>(work);
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(mix_backward_kernel<float>, dim3(blocks), dim3(kBlock), 0, stream, static_cast<const float*>(dy), static_cast<const float*>(u), static_cast<const float*>(c), mix_factor,
-                       static_cast<float*>(du), static_cast<float*>(dc), part, (long long)M, C, ld);
-  else
-    hipLaunchKernelGGL(mix_backward_kernel<bf16_t>, dim3(blocks), dim3(kBlock), 0, stream, static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(u), static_cast<const bf16_t*>(c), mix_factor,
-                       static_cast<bf16_t*>(du), static_cast<bf16_t*>(dc), part, (long long)M, C, ld);
-  VT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mix_finish_kernel, dim3(1), dim3(64), 0, stream, part, blocks, mix_factor, dmix);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const int rc = vt_dispatch<float, bf16_t>(dtype, [&](auto t) {
+    using T = vt_t<decltype(t)>;
+    return launch(mix_backward_kernel<T>, dim3(blocks), dim3(kBlock), 0, stream, static_cast<const T*>(dy), static_cast<const T*>(u), static_cast<const T*>(c), mix_factor,
+                  static_cast<T*>(du), static_cast<T*>(dc), part, (long long)M, C, ld);
+  });
+  if (rc != VT_OK) return rc;
+  return launch(mix_finish_kernel, dim3(1), dim3(64), 0, stream, part, blocks, mix_factor, dmix);
 }
 
 extern "C" int vt_time_lerp2x_backward(const void* dy, void* dx, int32_t dtype, int32_t B, int32_t Ti, int64_t HWC, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(dy && dx && B > 0 && Ti > 0 && HWC > 0 && (int64_t)B * Ti < 65536 && grad_dtype_ok(dtype), "vt_time_lerp2x_backward: bad arguments");
   const dim3 grid(grid_for(HWC, kBlock, 1024), (unsigned)(B * Ti));
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(time_lerp2x_backward_kernel<float>, grid, dim3(kBlock), 0, stream, static_cast<const float*>(dy), static_cast<float*>(dx), B, Ti, (long long)HWC);
-  else
-    hipLaunchKernelGGL(time_lerp2x_backward_kernel<bf16_t>, grid, dim3(kBlock), 0, stream, static_cast<const bf16_t*>(dy), static_cast<bf16_t*>(dx), B, Ti, (long long)HWC);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch<float, bf16_t>(dtype, [&](auto t) {
+    using T = vt_t<decltype(t)>;
+    return launch(time_lerp2x_backward_kernel<T>, grid, dim3(kBlock), 0, as_stream(stream_), static_cast<const T*>(dy), static_cast<T*>(dx), B, Ti, (long long)HWC);
+  });
 }
 
 extern "C" int vt_grad_ncthw_to_ndhwc(const float* x, void* y, int32_t out_dtype, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W, int32_t ldy, int32_t tpad,
                                       vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(x && y && B > 0 && C > 0 && T > 0 && H > 0 && W > 0 && ldy >= C && tpad >= 0 && grad_dtype_ok(out_dtype), "vt_grad_ncthw_to_ndhwc: bad arguments");
-  const unsigned grid = grid_for((long long)B * (T + tpad) * H * W);
-  if (out_dtype == VT_F32) hipLaunchKernelGGL(grad_ncthw_to_ndhwc_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, x, static_cast<float*>(y), B, C, T, H, W, ldy, tpad);
-  else hipLaunchKernelGGL(grad_ncthw_to_ndhwc_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, x, static_cast<bf16_t*>(y), B, C, T, H, W, ldy, tpad);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch<float, bf16_t>(out_dtype, [&](auto t) {
+    using TO = vt_t<decltype(t)>;
+    return launch(grad_ncthw_to_ndhwc_kernel<TO>, dim3(grid_for((long long)B * (T + tpad) * H * W, kBlock, 16384)), dim3(kBlock), 0, as_stream(stream_), x, static_cast<TO*>(y), B,
+                  C, T, H, W, ldy, tpad);
+  });
 }
 
 extern "C" int vt_grad_add(const void* a, const void* b, void* out, int32_t dtype, int64_t n, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(a && b && out && n > 0 && grad_dtype_ok(dtype), "vt_grad_add: bad arguments");
-  const unsigned grid = grid_for(n);
-  if (dtype == VT_F32) hipLaunchKernelGGL(grad_add_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, static_cast<const float*>(a), static_cast<const float*>(b), static_cast<float*>(out), (long long)n);
-  else hipLaunchKernelGGL(grad_add_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, static_cast<const bf16_t*>(a), static_cast<const bf16_t*>(b), static_cast<bf16_t*>(out), (long long)n);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch<float, bf16_t>(dtype, [&](auto t) {
+    using T = vt_t<decltype(t)>;
+    return launch(grad_add_kernel<T>, dim3(grid_for(n, kBlock, 16384)), dim3(kBlock), 0, as_stream(stream_), static_cast<const T*>(a), static_cast<const T*>(b), static_cast<T*>(out),
+                  (long long)n);
+  });
 }

@@ -10,7 +10,7 @@
 // Statistics: sum and sum of squares accumulated in fp64 (per-thread fp32 partials over <= 64 elements, fp64 block
 // reduction, one fp64 atomic per workgroup and group) -- domains reach 5 M elements, an fp32 E[x^2]-E[x]^2 would not
 // hold 1e-3.  PIXEL domains are tiny (T x C/G) and are reduced inside the apply kernel.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -121,27 +121,14 @@ __global__ __launch_bounds__(kBlock) void gn_pixel_kernel(const TI* __restrict__
   }
 }
 
-inline unsigned grid_for(long long n) {
-  long long b = (n + kBlock - 1) / kBlock;
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 template <typename TI, typename TO>
 int launch_groupnorm(const void* x, long long ldx, void* y, long long ldy, const float* gamma, const float* beta, int B,
                      int T, long long HW, int C, int G, int scope, float eps, int silu, double* work, hipStream_t stream) {
   const int cg = C / G;
   if (scope == VT_GN_PIXEL) {
-    const long long n = (long long)B * HW * G;
-    if (silu)
-      hipLaunchKernelGGL((gn_pixel_kernel<TI, TO, true>), dim3(grid_for(n)), dim3(kBlock), 0, stream, (const TI*)x, ldx, (TO*)y,
-                         ldy, gamma, beta, B, T, HW, G, cg, eps);
-    else
-      hipLaunchKernelGGL((gn_pixel_kernel<TI, TO, false>), dim3(grid_for(n)), dim3(kBlock), 0, stream, (const TI*)x, ldx, (TO*)y,
-                         ldy, gamma, beta, B, T, HW, G, cg, eps);
-    VT_CHECK_LAUNCH();
-    return VT_OK;
+    const dim3 grid(grid_for((long long)B * HW * G, kBlock, 4096));
+    return silu ? launch(gn_pixel_kernel<TI, TO, true>, grid, dim3(kBlock), 0, stream, (const TI*)x, ldx, (TO*)y, ldy, gamma, beta, B, T, HW, G, cg, eps)
+                : launch(gn_pixel_kernel<TI, TO, false>, grid, dim3(kBlock), 0, stream, (const TI*)x, ldx, (TO*)y, ldy, gamma, beta, B, T, HW, G, cg, eps);
   }
   const long long ninst = scope == VT_GN_FRAME ? (long long)B * T : B;
   const long long P = scope == VT_GN_FRAME ? HW : (long long)T * HW;
@@ -149,21 +136,13 @@ int launch_groupnorm(const void* x, long long ldx, void* y, long long ldy, const
   VT_CHECK_ARG(ninst <= 65535, "vt_groupnorm_act: too many instances (%lld)", ninst);
   VT_CHECK_HIP(hipMemsetAsync(work, 0, (size_t)ninst * G * 2 * sizeof(double), stream));
   const int slots = kBlock / G;
-  long long chunks = (P + slots * 8 - 1) / (slots * 8);      // ~8 pixels per thread and flush
-  if (chunks > 1024) chunks = 1024;
-  if (chunks < 1) chunks = 1;
-  hipLaunchKernelGGL(gn_stats_kernel<TI>, dim3((unsigned)chunks, (unsigned)ninst), dim3(kBlock), 0, stream, (const TI*)x, ldx,
-                     work, P, G, cg);
-  VT_CHECK_LAUNCH();
+  const unsigned chunks = grid_for(P, slots * 8, 1024);      // ~8 pixels per thread and flush
+  const int rc = launch(gn_stats_kernel<TI>, dim3(chunks, (unsigned)ninst), dim3(kBlock), 0, stream, (const TI*)x, ldx, work, P, G, cg);
+  if (rc != VT_OK) return rc;
   const long long M = ninst * P;
-  if (silu)
-    hipLaunchKernelGGL((gn_apply_kernel<TI, TO, true>), dim3(grid_for(M * (C / 4))), dim3(kBlock), 0, stream, (const TI*)x, ldx,
-                       (TO*)y, ldy, gamma, beta, (const double*)work, M, P, C, G, cg, eps);
-  else
-    hipLaunchKernelGGL((gn_apply_kernel<TI, TO, false>), dim3(grid_for(M * (C / 4))), dim3(kBlock), 0, stream, (const TI*)x, ldx,
-                       (TO*)y, ldy, gamma, beta, (const double*)work, M, P, C, G, cg, eps);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const dim3 grid(grid_for(M * (C / 4), kBlock, 4096));
+  return silu ? launch(gn_apply_kernel<TI, TO, true>, grid, dim3(kBlock), 0, stream, (const TI*)x, ldx, (TO*)y, ldy, gamma, beta, (const double*)work, M, P, C, G, cg, eps)
+              : launch(gn_apply_kernel<TI, TO, false>, grid, dim3(kBlock), 0, stream, (const TI*)x, ldx, (TO*)y, ldy, gamma, beta, (const double*)work, M, P, C, G, cg, eps);
 }
 
 }  // namespace
@@ -177,26 +156,14 @@ extern "C" int64_t vt_groupnorm_work_bytes(int32_t B, int32_t T, int32_t groups,
 extern "C" int vt_groupnorm_act(const void* x, int in_dtype, int64_t ldx, void* y, int out_dtype, int64_t ldy,
                                 const float* gamma, const float* beta, int32_t B, int32_t T, int64_t HW, int32_t C,
                                 int32_t groups, int32_t scope, float eps, int32_t silu, void* work, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(x && y && gamma && beta, "vt_groupnorm_act: null pointer");
   VT_CHECK_ARG(B > 0 && T > 0 && HW > 0 && C > 0 && ldx >= C && ldy >= C, "vt_groupnorm_act: bad dims");
   VT_CHECK_ARG(groups == 32 && C % groups == 0 && C % 4 == 0, "vt_groupnorm_act: needs 32 groups dividing C (C=%d)", C);
   VT_CHECK_ARG(scope >= VT_GN_FRAME && scope <= VT_GN_CLIP, "vt_groupnorm_act: scope %d", scope);
   double* w = reinterpret_cast<double*>(work);
-  if (in_dtype == VT_F32 && out_dtype == VT_F32)
-    return launch_groupnorm<float, float>(x, ldx, y, ldy, gamma, beta, B, T, HW, C, groups, scope, eps, silu, w, stream);
-  if (in_dtype == VT_BF16 && out_dtype == VT_BF16)
-    return launch_groupnorm<bf16_t, bf16_t>(x, ldx, y, ldy, gamma, beta, B, T, HW, C, groups, scope, eps, silu, w, stream);
-  if (in_dtype == VT_F32 && out_dtype == VT_BF16)
-    return launch_groupnorm<float, bf16_t>(x, ldx, y, ldy, gamma, beta, B, T, HW, C, groups, scope, eps, silu, w, stream);
-  if (in_dtype == VT_BF16 && out_dtype == VT_F32)
-    return launch_groupnorm<bf16_t, float>(x, ldx, y, ldy, gamma, beta, B, T, HW, C, groups, scope, eps, silu, w, stream);
-  if (in_dtype == VT_F16 && out_dtype == VT_F16)
-    return launch_groupnorm<f16_t, f16_t>(x, ldx, y, ldy, gamma, beta, B, T, HW, C, groups, scope, eps, silu, w, stream);
-  if (in_dtype == VT_F32 && out_dtype == VT_F16)
-    return launch_groupnorm<float, f16_t>(x, ldx, y, ldy, gamma, beta, B, T, HW, C, groups, scope, eps, silu, w, stream);
-  if (in_dtype == VT_F16 && out_dtype == VT_F32)
-    return launch_groupnorm<f16_t, float>(x, ldx, y, ldy, gamma, beta, B, T, HW, C, groups, scope, eps, silu, w, stream);
-  vt_set_error("vt_groupnorm_act: dtype combination %d -> %d", in_dtype, out_dtype);
-  return VT_ERR_ARG;
+  const int st = vt_dispatch_io(in_dtype, out_dtype, [&](auto ti, auto to) {
+    return launch_groupnorm<vt_t<decltype(ti)>, vt_t<decltype(to)>>(x, ldx, y, ldy, gamma, beta, B, T, HW, C, groups, scope, eps, silu, w, as_stream(stream_));
+  });
+  VT_CHECK_ARG(st != kNoMatch, "vt_groupnorm_act: dtype combination %d -> %d", in_dtype, out_dtype);
+  return st;
 }

@@ -4,9 +4,7 @@
 //   lpips_finish_kernel  the spatial means and their sum over the taps, fixed order
 // Deterministic by construction: the pixels of a (tap, pair) are cut into a fixed number of ranges that depends on the shape only,
 // every range is summed in a fixed order by one workgroup into its own workspace slot, and the finish adds the slots in order.
-#include <algorithm>
-
-#include "common.h"
+#include "launch.h"
 #include "row8.h"
 
 namespace {
@@ -173,20 +171,11 @@ int launch_tap(const void* feat, void* pooled, const float* lin_w, float* part, 
   const int slots = tap_slots(H, W);
   const int nq = ((H + 1) / 2) * ((W + 1) / 2);
   const int chunk = (nq + slots - 1) / slots;
-  const dim3 grid(slots, N), block(256);
-  const T* f = reinterpret_cast<const T*>(feat);
-  T* pl = reinterpret_cast<T*>(pooled);
-  switch (C) {
-    case 64: hipLaunchKernelGGL((lpips_tap_kernel<T, 64>), grid, block, 0, s, f, pl, lin_w, part, N, H, W, chunk); break;
-    case 128: hipLaunchKernelGGL((lpips_tap_kernel<T, 128>), grid, block, 0, s, f, pl, lin_w, part, N, H, W, chunk); break;
-    case 256: hipLaunchKernelGGL((lpips_tap_kernel<T, 256>), grid, block, 0, s, f, pl, lin_w, part, N, H, W, chunk); break;
-    default: hipLaunchKernelGGL((lpips_tap_kernel<T, 512>), grid, block, 0, s, f, pl, lin_w, part, N, H, W, chunk); break;
-  }
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch_int<64, 128, 256, 512>(C, [&](auto c) {
+    return launch(lpips_tap_kernel<T, decltype(c)::value>, dim3(slots, N), dim3(256), 0, s, reinterpret_cast<const T*>(feat), reinterpret_cast<T*>(pooled), lin_w, part,
+                  N, H, W, chunk);
+  });
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -206,16 +195,10 @@ extern "C" int vt_lpips_prep(const float* x, const float* y, void* out, const fl
   const int N = B * T;
   const long long HW = (long long)H * W;
   const long long total = 2ll * N * HW;
-  const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 65536);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(lpips_prep_kernel<float>, dim3(grid), dim3(256), 0, s, x, y, reinterpret_cast<float*>(out), shift, scale, N, T, HW, flags);
-  else if (dtype == VT_BF16)
-    hipLaunchKernelGGL(lpips_prep_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, x, y, reinterpret_cast<bf16_t*>(out), shift, scale, N, T, HW, flags);
-  else
-    hipLaunchKernelGGL(lpips_prep_kernel<f16_t>, dim3(grid), dim3(256), 0, s, x, y, reinterpret_cast<f16_t*>(out), shift, scale, N, T, HW, flags);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch<float, bf16_t, f16_t>(dtype, [&](auto t) {
+    using TO = vt_t<decltype(t)>;
+    return launch(lpips_prep_kernel<TO>, dim3(grid_for(total, 256, 65536)), dim3(256), 0, as_stream(stream), x, y, reinterpret_cast<TO*>(out), shift, scale, N, T, HW, flags);
+  });
 }
 
 extern "C" int vt_lpips_tap(const void* feat, void* pooled, const float* lin_w, void* work, int64_t work_bytes, int32_t dtype, int32_t N,
@@ -223,17 +206,16 @@ extern "C" int vt_lpips_tap(const void* feat, void* pooled, const float* lin_w, 
   VT_CHECK_ARG(dtype == VT_F32 || dtype == VT_BF16 || dtype == VT_F16, "vt_lpips_tap: dtype %d (VT_F32, VT_BF16 or VT_F16)", dtype);
   VT_CHECK_ARG(C == 64 || C == 128 || C == 256 || C == 512, "vt_lpips_tap: C=%d (64, 128, 256 or 512)", C);
   VT_CHECK_ARG(feat && lin_w && work, "vt_lpips_tap: null pointer");
-  VT_CHECK_ARG(aligned16(feat) && aligned16(lin_w) && aligned16(work) && (pooled == nullptr || aligned16(pooled)),
+  VT_CHECK_ARG(aligned16(feat, lin_w, work, pooled),
                "vt_lpips_tap: feat, pooled, lin_w and work must be 16-byte aligned");
   VT_CHECK_ARG(tap >= 0 && tap < kTaps, "vt_lpips_tap: tap %d (0..4)", tap);
   VT_CHECK_ARG(N > 0 && H > 0 && W > 0 && N <= 65535, "vt_lpips_tap: N=%d H=%d W=%d", N, H, W);
   VT_CHECK_ARG(work_bytes >= (int64_t)kTaps * N * kSlots * (int64_t)sizeof(float), "vt_lpips_tap: workspace %lld B < %lld B",
                (long long)work_bytes, (long long)kTaps * N * kSlots * (long long)sizeof(float));
   float* part = reinterpret_cast<float*>(work) + (long long)tap * N * kSlots;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VT_F32) return launch_tap<float>(feat, pooled, lin_w, part, N, H, W, C, s);
-  if (dtype == VT_BF16) return launch_tap<bf16_t>(feat, pooled, lin_w, part, N, H, W, C, s);
-  return launch_tap<f16_t>(feat, pooled, lin_w, part, N, H, W, C, s);
+  return vt_dispatch<float, bf16_t, f16_t>(dtype, [&](auto t) {
+    return launch_tap<vt_t<decltype(t)>>(feat, pooled, lin_w, part, N, H, W, C, as_stream(stream));
+  });
 }
 
 extern "C" int vt_lpips_finish(const void* work, int64_t work_bytes, float* lpips, float* tap_means, int32_t N, int32_t H, int32_t W,
@@ -251,8 +233,5 @@ extern "C" int vt_lpips_finish(const void* work, int64_t work_bytes, float* lpip
     h >>= 1;
     w >>= 1;
   }
-  hipLaunchKernelGGL(lpips_finish_kernel, dim3((N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const float*>(work), lpips, tap_means, N, geo);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(lpips_finish_kernel, dim3((N + 255) / 256), dim3(256), 0, as_stream(stream), reinterpret_cast<const float*>(work), lpips, tap_means, N, geo);
 }

@@ -6,9 +6,7 @@
 //   lpips_prep_backward_kernel  adjoint of the ScalingLayer + layout change: [N][H][W][8] -> fp32 [N][3][H][W]
 // No atomics, no cross-workgroup sums: every output element is written once by one lane, the channel sums of a pixel are DPP sums in
 // a fixed order, so two runs give the same bits.  Nothing allocates or synchronises.
-#include <algorithm>
-
-#include "common.h"
+#include "launch.h"
 #include "row8.h"
 
 namespace {
@@ -144,24 +142,12 @@ template <typename T, typename TP>
 int launch_tap_backward(const void* feat, const float* lin_w, const float* gout, const void* dpool, void* dfeat, int N, int H, int W, int C,
                         hipStream_t s) {
   const int nq = ((H + 1) / 2) * ((W + 1) / 2);
-  const int G = 256 / (C / 8);
-  const dim3 grid((unsigned)std::min((nq + G - 1) / G, 2048), N), block(256);
-  const T* f = reinterpret_cast<const T*>(feat);
-  const TP* dp = reinterpret_cast<const TP*>(dpool);
-  T* o = reinterpret_cast<T*>(dfeat);
-  switch (C) {
-    case 64: hipLaunchKernelGGL((lpips_tap_backward_kernel<T, TP, 64>), grid, block, 0, s, f, lin_w, gout, dp, o, N, H, W); break;
-    case 128: hipLaunchKernelGGL((lpips_tap_backward_kernel<T, TP, 128>), grid, block, 0, s, f, lin_w, gout, dp, o, N, H, W); break;
-    case 256: hipLaunchKernelGGL((lpips_tap_backward_kernel<T, TP, 256>), grid, block, 0, s, f, lin_w, gout, dp, o, N, H, W); break;
-    default: hipLaunchKernelGGL((lpips_tap_backward_kernel<T, TP, 512>), grid, block, 0, s, f, lin_w, gout, dp, o, N, H, W); break;
-  }
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const dim3 grid(grid_for(nq, 256 / (C / 8), 2048), N);
+  return vt_dispatch_int<64, 128, 256, 512>(C, [&](auto c) {
+    return launch(lpips_tap_backward_kernel<T, TP, decltype(c)::value>, grid, dim3(256), 0, s, reinterpret_cast<const T*>(feat), lin_w, gout,
+                  reinterpret_cast<const TP*>(dpool), reinterpret_cast<T*>(dfeat), N, H, W);
+  });
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool grad_dtype_ok(int dt) { return dt == VT_F32 || dt == VT_BF16; }
-inline unsigned grid_for(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 16384)); }
 
 }  // namespace
 
@@ -171,31 +157,26 @@ extern "C" int vt_lpips_tap_backward(const void* feat, const float* lin_w, const
   VT_CHECK_ARG(C == 64 || C == 128 || C == 256 || C == 512, "vt_lpips_tap_backward: C=%d (64, 128, 256 or 512)", C);
   VT_CHECK_ARG(feat && lin_w && gout && dfeat, "vt_lpips_tap_backward: null pointer");
   VT_CHECK_ARG(dpool == nullptr || dpool_dtype == dtype || dpool_dtype == VT_F32, "vt_lpips_tap_backward: dpool_dtype %d (dtype or VT_F32)", dpool_dtype);
-  VT_CHECK_ARG(aligned16(feat) && aligned16(lin_w) && aligned16(dfeat) && aligned16(dpool),
+  VT_CHECK_ARG(aligned16(feat, lin_w, dfeat, dpool),
                "vt_lpips_tap_backward: feat, lin_w, dpool and dfeat must be 16-byte aligned");
   VT_CHECK_ARG(N > 0 && H > 0 && W > 0 && N <= 65535 && (long long)H * W < (1ll << 30), "vt_lpips_tap_backward: N=%d H=%d W=%d", N, H, W);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VT_F32) return launch_tap_backward<float, float>(feat, lin_w, gout, dpool, dfeat, N, H, W, C, s);
-  if (dpool != nullptr && dpool_dtype == VT_F32) return launch_tap_backward<bf16_t, float>(feat, lin_w, gout, dpool, dfeat, N, H, W, C, s);
-  return launch_tap_backward<bf16_t, bf16_t>(feat, lin_w, gout, dpool, dfeat, N, H, W, C, s);
+  return vt_dispatch_grad(dtype, dpool != nullptr ? dpool_dtype : dtype, [&](auto t, auto tp) {
+    return launch_tap_backward<vt_t<decltype(t)>, vt_t<decltype(tp)>>(feat, lin_w, gout, dpool, dfeat, N, H, W, C, as_stream(stream));
+  });
 }
 
 extern "C" int vt_relu_backward(const void* dy, int32_t dy_dtype, const void* y, void* dx, int32_t dtype, int64_t n, vt_stream stream) {
   VT_CHECK_ARG(grad_dtype_ok(dtype) && (dy_dtype == dtype || dy_dtype == VT_F32), "vt_relu_backward: dy_dtype %d, dtype %d (fp32 or bf16; dy in dtype or fp32)",
                dy_dtype, dtype);
   VT_CHECK_ARG(dy && y && dx && n > 0 && n % 8 == 0, "vt_relu_backward: null pointer or n=%lld (a positive multiple of 8)", (long long)n);
-  VT_CHECK_ARG(aligned16(dy) && aligned16(y) && aligned16(dx), "vt_relu_backward: dy, y and dx must be 16-byte aligned");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  VT_CHECK_ARG(aligned16(dy, y, dx), "vt_relu_backward: dy, y and dx must be 16-byte aligned");
   const long long n8 = n / 8;
-  const dim3 grid(grid_for(n8)), block(256);
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL((relu_backward_kernel<float, float>), grid, block, 0, s, static_cast<const float*>(dy), static_cast<const float*>(y), static_cast<float*>(dx), n8);
-  else if (dy_dtype == VT_F32)
-    hipLaunchKernelGGL((relu_backward_kernel<float, bf16_t>), grid, block, 0, s, static_cast<const float*>(dy), static_cast<const bf16_t*>(y), static_cast<bf16_t*>(dx), n8);
-  else
-    hipLaunchKernelGGL((relu_backward_kernel<bf16_t, bf16_t>), grid, block, 0, s, static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(y), static_cast<bf16_t*>(dx), n8);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch_grad(dtype, dy_dtype, [&](auto t, auto ts) {
+    using T = vt_t<decltype(t)>;
+    using TS = vt_t<decltype(ts)>;
+    return launch(relu_backward_kernel<TS, T>, dim3(grid_for(n8, 256, 16384)), dim3(256), 0, as_stream(stream), static_cast<const TS*>(dy), static_cast<const T*>(y),
+                  static_cast<T*>(dx), n8);
+  });
 }
 
 extern "C" int vt_lpips_prep_backward(const void* d, int32_t dtype, const float* scale, float* dtarget, int32_t N, int32_t H, int32_t W, vt_stream stream) {
@@ -203,13 +184,10 @@ extern "C" int vt_lpips_prep_backward(const void* d, int32_t dtype, const float*
   VT_CHECK_ARG(d && scale && dtarget, "vt_lpips_prep_backward: null pointer");
   VT_CHECK_ARG(aligned16(d), "vt_lpips_prep_backward: d must be 16-byte aligned");
   VT_CHECK_ARG(N > 0 && H > 0 && W > 0, "vt_lpips_prep_backward: N=%d H=%d W=%d", N, H, W);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long long HW = (long long)H * W;
-  const dim3 grid(grid_for((long long)N * HW)), block(256);
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(lpips_prep_backward_kernel<float>, grid, block, 0, s, static_cast<const float*>(d), scale, dtarget, N, HW);
-  else
-    hipLaunchKernelGGL(lpips_prep_backward_kernel<bf16_t>, grid, block, 0, s, static_cast<const bf16_t*>(d), scale, dtarget, N, HW);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch<float, bf16_t>(dtype, [&](auto t) {
+    using TS = vt_t<decltype(t)>;
+    return launch(lpips_prep_backward_kernel<TS>, dim3(grid_for((long long)N * HW, 256, 16384)), dim3(256), 0, as_stream(stream), static_cast<const TS*>(d), scale, dtarget,
+                  N, HW);
+  });
 }

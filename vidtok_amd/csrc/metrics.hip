@@ -8,7 +8,7 @@
 // SSIM map of one (frame, channel): the 42x42 input patches of x and y go to LDS once, the five
 // filtered moments (x, y, xx, yy, xy) are produced separably (row pass into LDS, column pass in
 // registers), the SSIM values are reduced in the workgroup and added to the per-frame accumulator.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -143,7 +143,7 @@ extern "C" int64_t vt_eval_work_floats(int32_t B, int32_t T) { return 2ll * B * 
 
 extern "C" int vt_eval_psnr_ssim(const float* x, const float* y, float* psnr, float* ssim, float* work, int32_t B,
                                  int32_t C, int32_t T, int32_t H, int32_t W, int32_t raw, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = as_stream(stream_);
   VT_CHECK_ARG(x && y && psnr && ssim && work && B > 0 && C > 0 && T > 0 && H > 0 && W > 0,
                "vt_eval_psnr_ssim: bad arguments");
   int f = (int)lrintf((float)(H < W ? H : W) / 256.0f);   // python round(): half to even, like lrintf
@@ -168,15 +168,12 @@ extern "C" int vt_eval_psnr_ssim(const float* x, const float* y, float* psnr, fl
   const long long HW = (long long)H * W;
   int chunks = (int)((HW + 65535) / 65536);
   if (chunks < 1) chunks = 1;
-  hipLaunchKernelGGL(sqerr_kernel, dim3((unsigned)(B * C * T * chunks)), dim3(256), 0, stream, x, y, sq, B, C, T, HW,
-                     chunks, (int)raw);
-  VT_CHECK_LAUNCH();
+  int rc = launch(sqerr_kernel, dim3((unsigned)(B * C * T * chunks)), dim3(256), 0, stream, x, y, sq, B, C, T, HW, chunks, (int)raw);
+  if (rc != VT_OK) return rc;
   const int tiles_x = (Wo + TILE - 1) / TILE, tiles_y = (Ho + TILE - 1) / TILE;
-  hipLaunchKernelGGL(ssim_kernel, dim3((unsigned)(B * C * T * tiles_x * tiles_y)), dim3(256), 0, stream, x, y, ss, gt, B,
-                     C, T, H, W, f, tiles_x, tiles_y, (int)raw);
-  VT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(metrics_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)sq,
-                     (const float*)ss, psnr, ssim, n, 1.0f / ((float)C * (float)HW), 1.0f / ((float)C * (float)Ho * (float)Wo));
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  rc = launch(ssim_kernel, dim3((unsigned)(B * C * T * tiles_x * tiles_y)), dim3(256), 0, stream, x, y, ss, gt, B,
+              C, T, H, W, f, tiles_x, tiles_y, (int)raw);
+  if (rc != VT_OK) return rc;
+  return launch(metrics_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)sq,
+                (const float*)ss, psnr, ssim, n, 1.0f / ((float)C * (float)HW), 1.0f / ((float)C * (float)Ho * (float)Wo));
 }

@@ -7,7 +7,7 @@
 // plain fp32 additions in a fixed tree order, (t0 + t1) + (t2 + t3) with absent terms left out, which is the order the host
 // statements produce (rows first, then columns), so the packed bits equal theirs.  Data movement + roundings: one-time work per
 // weight version, but done here the step's kernel table holds no foreign kernel.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -62,7 +62,6 @@ __global__ __launch_bounds__(256) void pack_conv_weight_kernel(const PackArgs p)
 
 extern "C" int vt_pack_conv_weight(const float* w, void* out, int32_t out_dtype, int32_t Cout, int32_t Cin, int32_t cin_p, int32_t taps_in,
                                    int32_t taps_out, const int32_t* mix_host, int64_t ldw, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(w && out && Cout > 0 && Cin > 0 && cin_p >= Cin && taps_in > 0 && taps_out > 0, "vt_pack_conv_weight: bad arguments");
   VT_CHECK_ARG(out_dtype == VT_F32 || out_dtype == VT_BF16 || out_dtype == VT_F16 || out_dtype == VT_BF16X3, "vt_pack_conv_weight: out_dtype %d", out_dtype);
   VT_CHECK_ARG(taps_out <= kMaxTaps && (mix_host != nullptr || taps_out == taps_in), "vt_pack_conv_weight: at most %d taps; without a mix table taps_out = taps_in", kMaxTaps);
@@ -83,9 +82,5 @@ extern "C" int vt_pack_conv_weight(const float* w, void* out, int32_t out_dtype,
     }
     VT_CHECK_ARG(p.mix[j][0] >= 0 && !(p.mix[j][3] >= 0 && p.mix[j][2] < 0), "vt_pack_conv_weight: mix[%d] needs its first term (and term 2 before term 3)", j);
   }
-  const long long n = (long long)Cout * ldw;
-  const unsigned grid = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-  hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(grid), dim3(256), 0, stream, p);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(pack_conv_weight_kernel, dim3(grid_for((long long)Cout * ldw, 256, 8192)), dim3(256), 0, as_stream(stream_), p);
 }

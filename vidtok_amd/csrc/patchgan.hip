@@ -4,8 +4,7 @@
 // Rows are NDHWC pixels [M][ld]; a lane owns 8 consecutive channels of a row (row8.h), a workgroup walks a fixed range of rows.  Every
 // sum over rows is a per-workgroup partial in the caller's `work`, added in index order by a second launch (fp64 in that launch): no
 // atomics, two runs give the same bits, nothing allocates or synchronises.
-#include <algorithm>
-
+#include "launch.h"
 #include "row8.h"
 
 namespace {
@@ -14,14 +13,10 @@ constexpr int kBlock = 256;
 constexpr int kMaxC = 512;              // a lane per 8 channels, up to 64 lanes a row
 constexpr int kMaxGroups = 1024;        // per-workgroup partials of one reduction
 
-inline bool pg_dtype_ok(int dt) { return dt == VT_F32 || dt == VT_BF16; }
-inline int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
-
 // rows walked side by side by one workgroup (nq lanes a row), and the workgroups of a reduction over M rows
 inline int rows_par(int nq) { return kBlock / nq; }
 inline int64_t reduce_groups(int64_t M, int nq) {
-  const int64_t per = (int64_t)rows_par(nq) * 8;
-  return std::max<int64_t>(1, std::min<int64_t>((M + per - 1) / per, kMaxGroups));
+  return grid_for(M, rows_par(nq) * 8, kMaxGroups);
 }
 
 // the pre-activation of a normalised channel: ONE expression for the forward and the backward's sign mask
@@ -251,8 +246,6 @@ __global__ __launch_bounds__(kBlock) void leaky_bwd_kernel(const TD* __restrict_
   }
 }
 
-inline unsigned grid_for(int64_t n, int64_t cap = 16384) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap)); }
-
 }  // namespace
 
 extern "C" int64_t vt_batchnorm_stats_work_bytes(int64_t M, int32_t C) {
@@ -262,12 +255,12 @@ extern "C" int64_t vt_batchnorm_stats_work_bytes(int64_t M, int32_t C) {
 
 extern "C" int vt_batchnorm_stats(const void* x, int32_t dtype, int64_t ld, int64_t M, int32_t C, float eps, float* mean, float* var, float* rstd, void* work,
                                   int64_t work_bytes, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = as_stream(stream_);
   VT_CHECK_ARG(x && mean && var && work, "vt_batchnorm_stats: null pointer");
-  VT_CHECK_ARG(pg_dtype_ok(dtype), "vt_batchnorm_stats: dtype %d (F32 or BF16)", dtype);
+  VT_CHECK_ARG(grad_dtype_ok(dtype), "vt_batchnorm_stats: dtype %d (F32 or BF16)", dtype);
   VT_CHECK_ARG(M > 0 && C > 0 && C <= kMaxC && ld % 8 == 0 && ld >= (C + 7) / 8 * 8, "vt_batchnorm_stats: bad dims (M=%lld C=%d ld=%lld; C <= 512, ld a multiple of 8)",
                (long long)M, C, (long long)ld);
-  VT_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(work) & 15) == 0, "vt_batchnorm_stats: tensors must be 16-byte aligned");
+  VT_CHECK_ARG(aligned16(x, work), "vt_batchnorm_stats: tensors must be 16-byte aligned");
   const int nq = (C + 7) / 8;
   const int64_t groups = reduce_groups(M, nq);
   VT_CHECK_ARG(work_bytes >= align256(groups * 2 * C * 8), "vt_batchnorm_stats: workspace of %lld bytes, need %lld (vt_batchnorm_stats_work_bytes)",
@@ -275,33 +268,26 @@ extern "C" int vt_batchnorm_stats(const void* x, int32_t dtype, int64_t ld, int6
   const int64_t rows_per_wg = (M + groups - 1) / groups;
   const size_t lds = (size_t)rows_par(nq) * 2 * nq * 8 * sizeof(double);
   double* part = static_cast<double*>(work);
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(bn_stats_kernel<float>, dim3((unsigned)groups), dim3(kBlock), lds, stream, static_cast<const float*>(x), ld, M, C, nq, rows_per_wg, part);
-  else
-    hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, dim3((unsigned)groups), dim3(kBlock), lds, stream, static_cast<const bf16_t*>(x), ld, M, C, nq, rows_per_wg, part);
-  VT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((unsigned)((C + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, part, (int)groups, M, C, eps, mean, var, rstd);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const int rc = vt_dispatch<float, bf16_t>(dtype, [&](auto t) {
+    using T = vt_t<decltype(t)>;
+    return launch(bn_stats_kernel<T>, dim3((unsigned)groups), dim3(kBlock), lds, stream, static_cast<const T*>(x), ld, M, C, nq, rows_per_wg, part);
+  });
+  if (rc != VT_OK) return rc;
+  return launch(bn_stats_finish_kernel, dim3((unsigned)((C + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, part, (int)groups, M, C, eps, mean, var, rstd);
 }
 
 extern "C" int vt_batchnorm_act(const void* x, int32_t dtype, int64_t ld, void* y, int64_t ldy, const float* mean, const float* rstd, const float* gamma,
                                 const float* beta, float slope, int64_t M, int32_t C, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(x && y && mean && rstd && gamma && beta, "vt_batchnorm_act: null pointer");
-  VT_CHECK_ARG(pg_dtype_ok(dtype), "vt_batchnorm_act: dtype %d (F32 or BF16)", dtype);
+  VT_CHECK_ARG(grad_dtype_ok(dtype), "vt_batchnorm_act: dtype %d (F32 or BF16)", dtype);
   VT_CHECK_ARG(M > 0 && C > 0 && ld % 8 == 0 && ldy % 8 == 0 && ld >= (C + 7) / 8 * 8 && ldy >= C, "vt_batchnorm_act: bad dims (M=%lld C=%d ld=%lld ldy=%lld; strides multiples of 8)",
                (long long)M, C, (long long)ld, (long long)ldy);
-  VT_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0, "vt_batchnorm_act: tensors must be 16-byte aligned");
-  const unsigned grid = grid_for(M * (ldy / 8));
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(bn_act_kernel<float>, dim3(grid), dim3(kBlock), 0, stream, static_cast<const float*>(x), ld, static_cast<float*>(y), ldy, mean, rstd, gamma, beta,
-                       slope, M, C);
-  else
-    hipLaunchKernelGGL(bn_act_kernel<bf16_t>, dim3(grid), dim3(kBlock), 0, stream, static_cast<const bf16_t*>(x), ld, static_cast<bf16_t*>(y), ldy, mean, rstd, gamma,
-                       beta, slope, M, C);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  VT_CHECK_ARG(aligned16(x, y), "vt_batchnorm_act: tensors must be 16-byte aligned");
+  return vt_dispatch<float, bf16_t>(dtype, [&](auto t) {
+    using T = vt_t<decltype(t)>;
+    return launch(bn_act_kernel<T>, dim3(grid_for(M * (ldy / 8), kBlock, 16384)), dim3(kBlock), 0, as_stream(stream_), static_cast<const T*>(x), ld, static_cast<T*>(y), ldy,
+                  mean, rstd, gamma, beta, slope, M, C);
+  });
 }
 
 extern "C" int64_t vt_batchnorm_act_backward_work_bytes(int64_t M, int32_t C) {
@@ -312,17 +298,16 @@ extern "C" int64_t vt_batchnorm_act_backward_work_bytes(int64_t M, int32_t C) {
 extern "C" int vt_batchnorm_act_backward(const void* x, const void* dy, int32_t dtype, int32_t dy_dtype, int64_t ld, int64_t lddy, void* dx, int64_t ldo,
                                          const float* mean, const float* rstd, const float* gamma, const float* beta, float slope, float* dgamma, float* dbeta,
                                          int64_t M, int32_t C, int32_t mode, void* work, int64_t work_bytes, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = as_stream(stream_);
   VT_CHECK_ARG(x && dy && dx && mean && rstd && gamma && beta && work, "vt_batchnorm_act_backward: null pointer");
-  VT_CHECK_ARG(pg_dtype_ok(dtype) && (dy_dtype == dtype || dy_dtype == VT_F32), "vt_batchnorm_act_backward: dtype %d (F32 or BF16), dy_dtype %d (dtype or F32)", dtype,
+  VT_CHECK_ARG(grad_dtype_ok(dtype) && (dy_dtype == dtype || dy_dtype == VT_F32), "vt_batchnorm_act_backward: dtype %d (F32 or BF16), dy_dtype %d (dtype or F32)", dtype,
                dy_dtype);
   VT_CHECK_ARG(mode == VT_BN_BATCH || mode == VT_BN_RUNNING, "vt_batchnorm_act_backward: mode %d (VT_BN_BATCH or VT_BN_RUNNING)", mode);
   const int64_t c8 = (C + 7) / 8 * 8;
   VT_CHECK_ARG(M > 0 && C > 0 && C <= kMaxC && ld % 8 == 0 && lddy % 8 == 0 && ldo % 8 == 0 && ld >= c8 && lddy >= c8 && ldo >= C,
                "vt_batchnorm_act_backward: bad dims (M=%lld C=%d ld=%lld lddy=%lld ldo=%lld; C <= 512, strides multiples of 8)", (long long)M, C, (long long)ld,
                (long long)lddy, (long long)ldo);
-  VT_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0 && (reinterpret_cast<uintptr_t>(dx) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(work) & 15) == 0, "vt_batchnorm_act_backward: tensors must be 16-byte aligned");
+  VT_CHECK_ARG(aligned16(x, dy, dx, work), "vt_batchnorm_act_backward: tensors must be 16-byte aligned");
   const int nq = (C + 7) / 8;
   const int64_t groups = reduce_groups(M, nq);
   const int64_t pbytes = align256(groups * 2 * C * 4);
@@ -333,47 +318,32 @@ extern "C" int vt_batchnorm_act_backward(const void* x, const void* dy, int32_t 
   const int64_t rows_per_wg = (M + groups - 1) / groups;
   const size_t lds = (size_t)rows_par(nq) * 2 * nq * 8 * sizeof(float);
   const bool need_sums = mode == VT_BN_BATCH || dgamma != nullptr || dbeta != nullptr;
-  const unsigned grid = grid_for(M * (ldo / 8));
   const int batch = mode == VT_BN_BATCH;
-#define VT_BN_BWD(T, TD)                                                                                                                                     \
-  do {                                                                                                                                                       \
-    if (need_sums) {                                                                                                                                         \
-      hipLaunchKernelGGL((bn_bwd_sums_kernel<T, TD>), dim3((unsigned)groups), dim3(kBlock), lds, stream, static_cast<const T*>(x), static_cast<const TD*>(dy), ld, \
-                         lddy, mean, rstd, gamma, beta, slope, M, C, nq, rows_per_wg, part);                                                                 \
-      hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)((C + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, part, (int)groups, C, sums, dgamma, dbeta); \
-    }                                                                                                                                                        \
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<T, TD>), dim3(grid), dim3(kBlock), 0, stream, static_cast<const T*>(x), static_cast<const TD*>(dy), ld, lddy,         \
-                       static_cast<T*>(dx), ldo, mean, rstd, gamma, beta, slope, sums, M, C, batch);                                                         \
-  } while (0)
-  if (dtype == VT_F32)
-    VT_BN_BWD(float, float);
-  else if (dy_dtype == VT_F32)
-    VT_BN_BWD(bf16_t, float);
-  else
-    VT_BN_BWD(bf16_t, bf16_t);
-#undef VT_BN_BWD
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch_grad(dtype, dy_dtype, [&](auto t, auto td) {
+    using T = vt_t<decltype(t)>;
+    using TD = vt_t<decltype(td)>;
+    if (need_sums) {
+      int rc = launch(bn_bwd_sums_kernel<T, TD>, dim3((unsigned)groups), dim3(kBlock), lds, stream, static_cast<const T*>(x), static_cast<const TD*>(dy), ld, lddy, mean,
+                      rstd, gamma, beta, slope, M, C, nq, rows_per_wg, part);
+      if (rc != VT_OK) return rc;
+      rc = launch(bn_bwd_reduce_kernel, dim3((unsigned)((C + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, part, (int)groups, C, sums, dgamma, dbeta);
+      if (rc != VT_OK) return rc;
+    }
+    return launch(bn_bwd_dx_kernel<T, TD>, dim3(grid_for(M * (ldo / 8), kBlock, 16384)), dim3(kBlock), 0, stream, static_cast<const T*>(x), static_cast<const TD*>(dy), ld,
+                  lddy, static_cast<T*>(dx), ldo, mean, rstd, gamma, beta, slope, sums, M, C, batch);
+  });
 }
 
 extern "C" int vt_leaky_relu_backward(const void* dy, int32_t dy_dtype, const void* y, void* dx, int32_t dtype, int64_t n, float slope, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(dy && y && dx && n > 0 && n % 8 == 0, "vt_leaky_relu_backward: null pointer or n = %lld not a positive multiple of 8", (long long)n);
-  VT_CHECK_ARG(pg_dtype_ok(dtype) && (dy_dtype == dtype || dy_dtype == VT_F32), "vt_leaky_relu_backward: dtype %d (F32 or BF16), dy_dtype %d (dtype or F32)", dtype,
+  VT_CHECK_ARG(grad_dtype_ok(dtype) && (dy_dtype == dtype || dy_dtype == VT_F32), "vt_leaky_relu_backward: dtype %d (F32 or BF16), dy_dtype %d (dtype or F32)", dtype,
                dy_dtype);
   VT_CHECK_ARG(slope > 0.0f, "vt_leaky_relu_backward: slope %g: the sign of y is the sign of the pre-activation only for a positive slope", (double)slope);
-  VT_CHECK_ARG((reinterpret_cast<uintptr_t>(dy) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 && (reinterpret_cast<uintptr_t>(dx) & 15) == 0,
-               "vt_leaky_relu_backward: tensors must be 16-byte aligned");
-  const unsigned grid = grid_for(n / 8);
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL((leaky_bwd_kernel<float, float>), dim3(grid), dim3(kBlock), 0, stream, static_cast<const float*>(dy), static_cast<const float*>(y),
-                       static_cast<float*>(dx), slope, n / 8);
-  else if (dy_dtype == VT_F32)
-    hipLaunchKernelGGL((leaky_bwd_kernel<bf16_t, float>), dim3(grid), dim3(kBlock), 0, stream, static_cast<const float*>(dy), static_cast<const bf16_t*>(y),
-                       static_cast<bf16_t*>(dx), slope, n / 8);
-  else
-    hipLaunchKernelGGL((leaky_bwd_kernel<bf16_t, bf16_t>), dim3(grid), dim3(kBlock), 0, stream, static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(y),
-                       static_cast<bf16_t*>(dx), slope, n / 8);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  VT_CHECK_ARG(aligned16(dy, y, dx), "vt_leaky_relu_backward: tensors must be 16-byte aligned");
+  return vt_dispatch_grad(dtype, dy_dtype, [&](auto t, auto td) {
+    using T = vt_t<decltype(t)>;
+    using TD = vt_t<decltype(td)>;
+    return launch(leaky_bwd_kernel<T, TD>, dim3(grid_for(n / 8, kBlock, 16384)), dim3(kBlock), 0, as_stream(stream_), static_cast<const TD*>(dy), static_cast<const T*>(y),
+                  static_cast<T*>(dx), slope, n / 8);
+  });
 }

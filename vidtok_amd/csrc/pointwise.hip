@@ -6,7 +6,7 @@
 // innermost (NDHWC), so a wave touches whole 128-B lines; reductions over C never leave the
 // wave (sub-wave __shfl_xor trees, no LDS); grids are capped at ~2048 workgroups and
 // grid-stride the rest (guide G11).
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -186,23 +186,14 @@ int launch_layernorm(const void* x, long long ldx, void* y, long long ldy, const
       if (C == 8 * lp * r) { LP = lp; R = r; break; }
   VT_CHECK_ARG(LP != 0, "vt_layernorm_act: unsupported channel count C=%d (need C = 8*LP*R, LP in {4..64}, R in {1,2,4}, or C = 192)", C);
   const int groups = (kBlock / LP) * ((R == 1) ? 4 : 2);   // positions per workgroup and iteration
-  long long blocks = (M + groups - 1) / groups;
-  if (blocks > kMaxGrid) blocks = kMaxGrid;
-  if (blocks < 1) blocks = 1;
-#define VT_LN_CASE(lp, r)                                                                            \
-  if (LP == lp && R == r) {                                                                          \
-    if (silu)                                                                                        \
-      hipLaunchKernelGGL((layernorm_act_kernel<TI, TO, lp, r, true>), dim3((unsigned)blocks), dim3(kBlock), 0,  \
-                         stream, (const TI*)x, ldx, (TO*)y, ldy, gamma, beta, M, C, eps);             \
-    else                                                                                             \
-      hipLaunchKernelGGL((layernorm_act_kernel<TI, TO, lp, r, false>), dim3((unsigned)blocks), dim3(kBlock), 0, \
-                         stream, (const TI*)x, ldx, (TO*)y, ldy, gamma, beta, M, C, eps);             \
-    VT_CHECK_LAUNCH();                                                                               \
-    return VT_OK;                                                                                    \
-  }
-  VT_LN_CASE(64, 1) VT_LN_CASE(64, 2) VT_LN_CASE(64, 4)
-  VT_LN_CASE(32, 1) VT_LN_CASE(16, 1) VT_LN_CASE(8, 1) VT_LN_CASE(4, 1) VT_LN_CASE(8, 3)
-#undef VT_LN_CASE
+  const dim3 grid(grid_for(M, groups, kMaxGrid));
+  // the instantiated (LP, R) pairs, as the key 8 LP + R
+  const int st = vt_dispatch_int<64 * 8 + 1, 64 * 8 + 2, 64 * 8 + 4, 32 * 8 + 1, 16 * 8 + 1, 8 * 8 + 1, 4 * 8 + 1, 8 * 8 + 3>(LP * 8 + R, [&](auto key) {
+    constexpr int lp = decltype(key)::value / 8, r = decltype(key)::value % 8;
+    return silu ? launch(layernorm_act_kernel<TI, TO, lp, r, true>, grid, dim3(kBlock), 0, stream, (const TI*)x, ldx, (TO*)y, ldy, gamma, beta, M, C, eps)
+                : launch(layernorm_act_kernel<TI, TO, lp, r, false>, grid, dim3(kBlock), 0, stream, (const TI*)x, ldx, (TO*)y, ldy, gamma, beta, M, C, eps);
+  });
+  if (st != kNoMatch) return st;
   vt_set_error("vt_layernorm_act: no kernel for LP=%d R=%d", LP, R);
   return VT_ERR_UNSUPPORTED;
 }
@@ -364,39 +355,21 @@ __global__ __launch_bounds__(kBlock) void gather_frames_kernel(const VT* __restr
   }
 }
 
-inline unsigned grid_for(long long n) {
-  long long b = (n + kBlock - 1) / kBlock;
-  if (b > kMaxGrid) b = kMaxGrid;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 }  // namespace
 
 extern "C" int vt_layernorm_act(const void* x, int in_dtype, int64_t ldx, void* y, int out_dtype, int64_t ldy,
                                 const float* gamma, const float* beta, int64_t M, int32_t C, float eps,
                                 int32_t silu, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = as_stream(stream_);
   VT_CHECK_ARG(x && y && gamma && beta, "vt_layernorm_act: null pointer");
   VT_CHECK_ARG(M >= 0 && C > 0 && ldx >= C && ldy >= C, "vt_layernorm_act: bad dims");
   VT_CHECK_ARG(ldx % 8 == 0 && ldy % 8 == 0, "vt_layernorm_act: row strides must be multiples of 8");
   if (M == 0) return VT_OK;
-  if (in_dtype == VT_F32 && out_dtype == VT_F32)
-    return launch_layernorm<float, float>(x, ldx, y, ldy, gamma, beta, M, C, eps, silu, stream);
-  if (in_dtype == VT_BF16 && out_dtype == VT_BF16)
-    return launch_layernorm<bf16_t, bf16_t>(x, ldx, y, ldy, gamma, beta, M, C, eps, silu, stream);
-  if (in_dtype == VT_F32 && out_dtype == VT_BF16)
-    return launch_layernorm<float, bf16_t>(x, ldx, y, ldy, gamma, beta, M, C, eps, silu, stream);
-  if (in_dtype == VT_BF16 && out_dtype == VT_F32)
-    return launch_layernorm<bf16_t, float>(x, ldx, y, ldy, gamma, beta, M, C, eps, silu, stream);
-  if (in_dtype == VT_F16 && out_dtype == VT_F16)
-    return launch_layernorm<f16_t, f16_t>(x, ldx, y, ldy, gamma, beta, M, C, eps, silu, stream);
-  if (in_dtype == VT_F32 && out_dtype == VT_F16)
-    return launch_layernorm<float, f16_t>(x, ldx, y, ldy, gamma, beta, M, C, eps, silu, stream);
-  if (in_dtype == VT_F16 && out_dtype == VT_F32)
-    return launch_layernorm<f16_t, float>(x, ldx, y, ldy, gamma, beta, M, C, eps, silu, stream);
-  vt_set_error("vt_layernorm_act: dtype combination %d -> %d", in_dtype, out_dtype);
-  return VT_ERR_ARG;
+  const int st = vt_dispatch_io(in_dtype, out_dtype, [&](auto ti, auto to) {
+    return launch_layernorm<vt_t<decltype(ti)>, vt_t<decltype(to)>>(x, ldx, y, ldy, gamma, beta, M, C, eps, silu, stream);
+  });
+  VT_CHECK_ARG(st != kNoMatch, "vt_layernorm_act: dtype combination %d -> %d", in_dtype, out_dtype);
+  return st;
 }
 
 // tanh in place on an fp32 tensor: the `tanh_out` option of the decoders (model_3dcausal.py:866-869)
@@ -405,83 +378,54 @@ __global__ __launch_bounds__(256) void tanh_inplace_kernel(float* __restrict__ x
 }
 
 extern "C" int vt_tanh_inplace(float* x, int64_t n, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(x != nullptr && n >= 0, "vt_tanh_inplace: bad arguments");
   if (n == 0) return VT_OK;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(tanh_inplace_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, (long long)n);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(tanh_inplace_kernel, dim3(grid_for(n, 256, 65536)), dim3(256), 0, as_stream(stream_), x, (long long)n);
 }
 
 extern "C" int vt_softmax_rows(const float* s, void* p, int out_dtype, int64_t rows, int32_t cols, int64_t ldp,
                                float scale, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(s && p && rows >= 0 && cols > 0 && ldp >= cols, "vt_softmax_rows: bad arguments");
   if (rows == 0) return VT_OK;
-  long long blocks = (rows + 3) / 4;
-  if (blocks > 4096) blocks = 4096;
-  if (out_dtype == VT_F32)
-    hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, s, (float*)p,
-                       (long long)rows, cols, (long long)ldp, scale);
-  else if (out_dtype == VT_BF16)
-    hipLaunchKernelGGL(softmax_rows_kernel<bf16_t>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, s, (bf16_t*)p,
-                       (long long)rows, cols, (long long)ldp, scale);
-  else if (out_dtype == VT_F16)
-    hipLaunchKernelGGL(softmax_rows_kernel<f16_t>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, s, (f16_t*)p,
-                       (long long)rows, cols, (long long)ldp, scale);
-  else
-    VT_CHECK_ARG(false, "vt_softmax_rows: out_dtype %d", out_dtype);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const int st = vt_dispatch<float, bf16_t, f16_t>(out_dtype, [&](auto t) {
+    using TO = vt_t<decltype(t)>;
+    return launch(softmax_rows_kernel<TO>, dim3(grid_for(rows, kBlock / 64, 4096)), dim3(kBlock), 0, as_stream(stream_), s, (TO*)p,
+                  (long long)rows, cols, (long long)ldp, scale);
+  });
+  VT_CHECK_ARG(st != kNoMatch, "vt_softmax_rows: out_dtype %d", out_dtype);
+  return st;
 }
 
 extern "C" int vt_ncthw_to_ndhwc(const float* x, void* y, int out_dtype, int32_t B, int32_t C, int32_t T, int32_t H,
                                  int32_t W, int32_t ldy, int32_t tpad, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(x && y && B > 0 && C > 0 && T > 0 && H > 0 && W > 0 && ldy >= C && tpad >= 0,
                "vt_ncthw_to_ndhwc: bad arguments");
   const long long npix = (long long)B * (T + tpad) * H * W;
-  if (out_dtype == VT_F32)
-    hipLaunchKernelGGL(ncthw_to_ndhwc_kernel<float>, dim3(grid_for(npix)), dim3(kBlock), 0, stream, x, (float*)y, B, C,
-                       T, H, W, ldy, tpad);
-  else if (out_dtype == VT_BF16)
-    hipLaunchKernelGGL(ncthw_to_ndhwc_kernel<bf16_t>, dim3(grid_for(npix)), dim3(kBlock), 0, stream, x, (bf16_t*)y, B,
-                       C, T, H, W, ldy, tpad);
-  else if (out_dtype == VT_F16)
-    hipLaunchKernelGGL(ncthw_to_ndhwc_kernel<f16_t>, dim3(grid_for(npix)), dim3(kBlock), 0, stream, x, (f16_t*)y, B,
-                       C, T, H, W, ldy, tpad);
-  else
-    VT_CHECK_ARG(false, "vt_ncthw_to_ndhwc: out_dtype %d", out_dtype);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const int st = vt_dispatch<float, bf16_t, f16_t>(out_dtype, [&](auto t) {
+    using TO = vt_t<decltype(t)>;
+    return launch(ncthw_to_ndhwc_kernel<TO>, dim3(grid_for(npix, kBlock, kMaxGrid)), dim3(kBlock), 0, as_stream(stream_), x, (TO*)y, B, C,
+                  T, H, W, ldy, tpad);
+  });
+  VT_CHECK_ARG(st != kNoMatch, "vt_ncthw_to_ndhwc: out_dtype %d", out_dtype);
+  return st;
 }
 
 extern "C" int vt_ndhwc_to_ncthw(const void* x, int in_dtype, float* y, int32_t B, int32_t C, int32_t T, int32_t H,
                                  int32_t W, int32_t ldx, int32_t ttrim, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(x && y && B > 0 && C > 0 && T > 0 && H > 0 && W > 0 && ldx >= C && ttrim >= 0 && ttrim < T,
                "vt_ndhwc_to_ncthw: bad arguments");
   const long long n = (long long)B * C * (T - ttrim) * H * W;
-  if (in_dtype == VT_F32)
-    hipLaunchKernelGGL(ndhwc_to_ncthw_kernel<float>, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const float*)x, y, B,
-                       C, T, H, W, ldx, ttrim);
-  else if (in_dtype == VT_BF16)
-    hipLaunchKernelGGL(ndhwc_to_ncthw_kernel<bf16_t>, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const bf16_t*)x, y,
-                       B, C, T, H, W, ldx, ttrim);
-  else if (in_dtype == VT_F16)
-    hipLaunchKernelGGL(ndhwc_to_ncthw_kernel<f16_t>, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const f16_t*)x, y,
-                       B, C, T, H, W, ldx, ttrim);
-  else
-    VT_CHECK_ARG(false, "vt_ndhwc_to_ncthw: in_dtype %d", in_dtype);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const int st = vt_dispatch<float, bf16_t, f16_t>(in_dtype, [&](auto t) {
+    using TI = vt_t<decltype(t)>;
+    return launch(ndhwc_to_ncthw_kernel<TI>, dim3(grid_for(n, kBlock, kMaxGrid)), dim3(kBlock), 0, as_stream(stream_), (const TI*)x, y, B,
+                  C, T, H, W, ldx, ttrim);
+  });
+  VT_CHECK_ARG(st != kNoMatch, "vt_ndhwc_to_ncthw: in_dtype %d", in_dtype);
+  return st;
 }
 
 extern "C" int vt_time_avgpool3s2(const void* x, const void* cache, void* y, int dtype, int32_t B, int32_t Ti,
                                   int64_t HW, int32_t C, int32_t tmode, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   // To = Ti / 2 (floor): an odd Ti drops its last frame, as avg_pool3d(kernel 3, stride 2) over Ti + 1 padded frames does
   VT_CHECK_ARG(x && y && B > 0 && Ti >= 2 && HW > 0 && C > 0, "vt_time_avgpool3s2: bad dims (Ti=%d)", Ti);
   VT_CHECK_ARG((HW * C) % 4 == 0, "vt_time_avgpool3s2: frame size must be a multiple of 4 elements");
@@ -489,43 +433,30 @@ extern "C" int vt_time_avgpool3s2(const void* x, const void* cache, void* y, int
   VT_CHECK_ARG(tmode != VT_TPAD_CACHE || cache != nullptr, "vt_time_avgpool3s2: cache mode without cache");
   const long long F4 = HW * C / 4;
   const long long n = (long long)B * (Ti / 2) * F4;
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(time_avgpool3s2_kernel<float>, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const float*)x,
-                       (const float*)cache, (float*)y, B, Ti, F4, tmode);
-  else if (dtype == VT_BF16)
-    hipLaunchKernelGGL(time_avgpool3s2_kernel<bf16_t>, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const bf16_t*)x,
-                       (const bf16_t*)cache, (bf16_t*)y, B, Ti, F4, tmode);
-  else if (dtype == VT_F16)
-    hipLaunchKernelGGL(time_avgpool3s2_kernel<f16_t>, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const f16_t*)x,
-                       (const f16_t*)cache, (f16_t*)y, B, Ti, F4, tmode);
-  else
-    VT_CHECK_ARG(false, "vt_time_avgpool3s2: dtype %d", dtype);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const int st = vt_dispatch<float, bf16_t, f16_t>(dtype, [&](auto t) {
+    using T = vt_t<decltype(t)>;
+    return launch(time_avgpool3s2_kernel<T>, dim3(grid_for(n, kBlock, kMaxGrid)), dim3(kBlock), 0, as_stream(stream_), (const T*)x,
+                  (const T*)cache, (T*)y, B, Ti, F4, tmode);
+  });
+  VT_CHECK_ARG(st != kNoMatch, "vt_time_avgpool3s2: dtype %d", dtype);
+  return st;
 }
 
 extern "C" int vt_time_lerp2x_cat(const void* head, int32_t nh, const void* x, void* y, int dtype, int32_t B, int32_t Tx, int32_t skip,
                                   int64_t HWC, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(x && y && B > 0 && Tx > 0 && HWC > 0 && HWC % 4 == 0, "vt_time_lerp2x: bad dims");
   VT_CHECK_ARG(nh >= 0 && (nh == 0 || head != nullptr) && skip >= 0 && skip < 2 * (nh + Tx), "vt_time_lerp2x_cat: head frames %d, skip %d of %d", nh, skip, 2 * (nh + Tx));
   const long long F4 = HWC / 4;
   const int To = 2 * (nh + Tx) - skip;
   VT_CHECK_ARG((long long)B * To <= 65535, "vt_time_lerp2x: B * output frames = %lld > 65 535", (long long)B * To);
   const long long per = (long long)kBlock * (dtype == VT_F32 ? 1 : 2);                  // quads a workgroup moves per sweep of a frame
-  long long gx = (F4 + per - 1) / per;
-  if (gx > 1024) gx = 1024;
-  const dim3 grid((unsigned)gx, (unsigned)(B * To));
-  if (dtype == VT_F32)
-    hipLaunchKernelGGL(time_lerp2x_kernel<float>, grid, dim3(kBlock), 0, stream, (const float*)head, nh, (const float*)x, (float*)y, B, Tx, skip, F4);
-  else if (dtype == VT_BF16)
-    hipLaunchKernelGGL(time_lerp2x_kernel<bf16_t>, grid, dim3(kBlock), 0, stream, (const bf16_t*)head, nh, (const bf16_t*)x, (bf16_t*)y, B, Tx, skip, F4);
-  else if (dtype == VT_F16)
-    hipLaunchKernelGGL(time_lerp2x_kernel<f16_t>, grid, dim3(kBlock), 0, stream, (const f16_t*)head, nh, (const f16_t*)x, (f16_t*)y, B, Tx, skip, F4);
-  else
-    VT_CHECK_ARG(false, "vt_time_lerp2x: dtype %d", dtype);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const dim3 grid(grid_for(F4, per, 1024), (unsigned)(B * To));
+  const int st = vt_dispatch<float, bf16_t, f16_t>(dtype, [&](auto t) {
+    using T = vt_t<decltype(t)>;
+    return launch(time_lerp2x_kernel<T>, grid, dim3(kBlock), 0, as_stream(stream_), (const T*)head, nh, (const T*)x, (T*)y, B, Tx, skip, F4);
+  });
+  VT_CHECK_ARG(st != kNoMatch, "vt_time_lerp2x: dtype %d", dtype);
+  return st;
 }
 
 extern "C" int vt_time_lerp2x(const void* x, void* y, int dtype, int32_t B, int32_t Ti, int64_t HWC,
@@ -536,12 +467,10 @@ extern "C" int vt_time_lerp2x(const void* x, void* y, int dtype, int32_t B, int3
 extern "C" int vt_gather_frames(const void* src, void* dst, int32_t esize, int32_t B, int64_t frame_elems,
                                 int64_t src_bstride, int64_t dst_bstride, const int32_t* idx_host, int32_t n,
                                 vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(src && dst && idx_host && B > 0 && n > 0 && n <= 128 && frame_elems > 0,
                "vt_gather_frames: bad arguments (n=%d)", n);
   VT_CHECK_ARG(esize == 2 || esize == 4, "vt_gather_frames: esize %d", esize);
-  const bool v16 = (frame_elems * esize) % 16 == 0 && (src_bstride * esize) % 16 == 0 && (dst_bstride * esize) % 16 == 0 &&
-                   ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  const bool v16 = (frame_elems * esize) % 16 == 0 && (src_bstride * esize) % 16 == 0 && (dst_bstride * esize) % 16 == 0 && aligned16(src, dst);
   VT_CHECK_ARG(v16 || ((frame_elems * esize) % 4 == 0 && (src_bstride * esize) % 4 == 0 && (dst_bstride * esize) % 4 == 0 &&
                        ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3) == 0),
                "vt_gather_frames: frames, strides and pointers must be multiples of 4 bytes");
@@ -553,14 +482,9 @@ extern "C" int vt_gather_frames(const void* src, void* dst, int32_t esize, int32
   const int unit = v16 ? 16 : 4;
   const long long F16 = frame_elems * esize / unit;
   const long long total = (long long)B * n * F16;
-  if (v16)
-    hipLaunchKernelGGL(gather_frames_kernel<u32x4>, dim3(grid_for(total)), dim3(kBlock), 0, stream, (const u32x4*)src,
-                       (u32x4*)dst, B, F16, (long long)(src_bstride * esize / 16), (long long)(dst_bstride * esize / 16),
-                       gi, n);
-  else
-    hipLaunchKernelGGL(gather_frames_kernel<uint32_t>, dim3(grid_for(total)), dim3(kBlock), 0, stream, (const uint32_t*)src,
-                       (uint32_t*)dst, B, F16, (long long)(src_bstride * esize / 4), (long long)(dst_bstride * esize / 4),
-                       gi, n);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return vt_dispatch_size<u32x4, uint32_t>(unit, [&](auto t) {
+    using VT = vt_t<decltype(t)>;
+    return launch(gather_frames_kernel<VT>, dim3(grid_for(total, kBlock, kMaxGrid)), dim3(kBlock), 0, as_stream(stream_), (const VT*)src,
+                  (VT*)dst, B, F16, (long long)(src_bstride * esize / unit), (long long)(dst_bstride * esize / unit), gi, n);
+  });
 }

@@ -2,7 +2,7 @@
 // All tensors here are the small NCTHW fp32 latents of the reference API ([B][C][S], S = T*H*W).
 #include <math.h>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -306,13 +306,6 @@ int make_consts(const int32_t* levels, int D, FsqConsts* k) {
   return VT_OK;
 }
 
-inline unsigned grid_for(long long n) {
-  long long b = (n + kBlock - 1) / kBlock;
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 }  // namespace
 
 extern "C" int vt_fsq_consts(const int32_t* levels_host, int32_t D, float* out_host) {
@@ -331,24 +324,18 @@ extern "C" int vt_fsq_consts(const int32_t* levels_host, int32_t D, float* out_h
 
 extern "C" int vt_kl_sample(const float* h, const float* noise, float* z, float* kl_out, int32_t B, int32_t zc,
                             int64_t S, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(h && z && kl_out && B > 0 && zc > 0 && S > 0, "vt_kl_sample: bad arguments");
-  hipLaunchKernelGGL(kl_sample_kernel, dim3(1), dim3(1024), 0, stream, h, noise, z, kl_out, B, zc, (long long)S);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(kl_sample_kernel, dim3(1), dim3(1024), 0, as_stream(stream_), h, noise, z, kl_out, B, zc, (long long)S);
 }
 
 extern "C" int vt_fsq_quantize_cb(const float* h, float* z, int32_t* indices, const int32_t* levels_host, int32_t D,
                                   int32_t B, int32_t ncb, int64_t S, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(h && z && indices && B > 0 && S > 0 && ncb >= 1, "vt_fsq_quantize: bad arguments");
   FsqConsts k;
   int rc = make_consts(levels_host, D, &k);
   if (rc != VT_OK) return rc;
-  hipLaunchKernelGGL(fsq_quantize_kernel, dim3(grid_for((long long)B * ncb * S)), dim3(kBlock), 0, stream, h, z, indices, k,
-                     B * ncb, (long long)S, ncb);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(fsq_quantize_kernel, dim3(grid_for((long long)B * ncb * S, kBlock, 2048)), dim3(kBlock), 0, as_stream(stream_), h, z, indices, k,
+                B * ncb, (long long)S, ncb);
 }
 
 extern "C" int vt_fsq_quantize(const float* h, float* z, int32_t* indices, const int32_t* levels_host, int32_t D,
@@ -377,26 +364,20 @@ __global__ __launch_bounds__(kBlock) void channel_linear_kernel(const float* __r
 
 extern "C" int vt_channel_linear(const float* x, const float* w, const float* bias, float* y, int32_t B, int32_t Cin,
                                  int32_t Cout, int64_t S, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(x && w && y && B > 0 && Cin > 0 && Cout > 0 && S > 0 && Cin <= 1024 && Cout <= 1024,
                "vt_channel_linear: bad arguments");
-  hipLaunchKernelGGL(channel_linear_kernel, dim3(grid_for((long long)B * S)), dim3(kBlock), 0, stream, x, w, bias, y, B,
-                     Cin, Cout, (long long)S);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(channel_linear_kernel, dim3(grid_for((long long)B * S, kBlock, 2048)), dim3(kBlock), 0, as_stream(stream_), x, w, bias, y, B,
+                Cin, Cout, (long long)S);
 }
 
 extern "C" int vt_fsq_indices_to_codes_cb(const int32_t* indices, float* z, const int32_t* levels_host, int32_t D,
                                           int32_t B, int32_t ncb, int64_t S, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(indices && z && B > 0 && S > 0 && ncb >= 1, "vt_fsq_indices_to_codes: bad arguments");
   FsqConsts k;
   int rc = make_consts(levels_host, D, &k);
   if (rc != VT_OK) return rc;
-  hipLaunchKernelGGL(fsq_indices_to_codes_kernel, dim3(grid_for((long long)B * ncb * S)), dim3(kBlock), 0, stream, indices,
-                     z, k, B * ncb, (long long)S, ncb);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(fsq_indices_to_codes_kernel, dim3(grid_for((long long)B * ncb * S, kBlock, 2048)), dim3(kBlock), 0, as_stream(stream_), indices,
+                z, k, B * ncb, (long long)S, ncb);
 }
 
 extern "C" int vt_fsq_indices_to_codes(const int32_t* indices, float* z, const int32_t* levels_host, int32_t D,
@@ -430,25 +411,19 @@ __global__ void fsq_aux_loss_kernel(const float* __restrict__ st, const float* _
 
 extern "C" int vt_fsq_aux_loss(const float* stats3, const float* codebook_entropy, float diversity_gamma, float entropy_weight,
                                float commitment_weight, float* out, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(stats3 && out, "vt_fsq_aux_loss: null argument");
-  hipLaunchKernelGGL(fsq_aux_loss_kernel, dim3(1), dim3(64), 0, stream, stats3, codebook_entropy, diversity_gamma, entropy_weight,
-                     commitment_weight, out);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(fsq_aux_loss_kernel, dim3(1), dim3(64), 0, as_stream(stream_), stats3, codebook_entropy, diversity_gamma, entropy_weight,
+                commitment_weight, out);
 }
 
 extern "C" int vt_entropy(const float* avg, int64_t J, float* out, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(avg && out && J > 0, "vt_entropy: bad arguments");
-  hipLaunchKernelGGL(entropy_kernel, dim3(1), dim3(kBlock), 0, stream, avg, (long long)J, out);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(entropy_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream_), avg, (long long)J, out);
 }
 
 extern "C" int vt_fsq_aux_stats_avg(const float* h, const int32_t* levels_host, int32_t D, int32_t B, int64_t S,
                                     float inv_temperature, float* work, float* out3, float* avg_out, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = as_stream(stream_);
   VT_CHECK_ARG(h && work && out3 && B > 0 && S > 0, "vt_fsq_aux_stats: bad arguments");
   FsqConsts k;
   int rc = make_consts(levels_host, D, &k);
@@ -460,22 +435,19 @@ extern "C" int vt_fsq_aux_stats_avg(const float* h, const int32_t* levels_host, 
   float* tables = work;
   float* accum = work + ntok * D * kMaxL;
   VT_CHECK_HIP(hipMemsetAsync(accum, 0, 4 * sizeof(float), stream));
-  hipLaunchKernelGGL(fsq_aux_tables_kernel, dim3(grid_for(ntok)), dim3(kBlock), 0, stream, h, k, B, (long long)S,
-                     inv_temperature, tables, accum);
-  VT_CHECK_LAUNCH();
+  rc = launch(fsq_aux_tables_kernel, dim3(grid_for(ntok, kBlock, 2048)), dim3(kBlock), 0, stream, h, k, B, (long long)S,
+              inv_temperature, tables, accum);
+  if (rc != VT_OK) return rc;
   float* part = accum + 4;
   const FsqSplit sp = fsq_split(k);
   VT_CHECK_ARG(sp.JL <= 2 * kBlock, "vt_fsq_aux_stats: first level %d too large", levels_host[0]);
   const long long tile_tokens = (ntok + kTokTiles - 1) / kTokTiles;
   const int ntiles = (int)((ntok + tile_tokens - 1) / tile_tokens);
-  hipLaunchKernelGGL(fsq_aux_pairs_kernel, dim3((unsigned)ntiles, (unsigned)((sp.JH + kHiChunk - 1) / kHiChunk)), dim3(kBlock), 0, stream,
-                     (const float*)tables, k, sp, ntok, tile_tokens, (int)J, part, accum);
-  VT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(fsq_aux_reduce_kernel, dim3((unsigned)((J + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, (const float*)part,
-                     ntiles, (int)J, ntok, accum, avg_out);
-  VT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(fsq_aux_finish_kernel, dim3(1), dim3(1), 0, stream, (const float*)accum, ntok,
-                     ntok * (long long)D, out3);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  rc = launch(fsq_aux_pairs_kernel, dim3((unsigned)ntiles, (unsigned)((sp.JH + kHiChunk - 1) / kHiChunk)), dim3(kBlock), 0, stream,
+              (const float*)tables, k, sp, ntok, tile_tokens, (int)J, part, accum);
+  if (rc != VT_OK) return rc;
+  rc = launch(fsq_aux_reduce_kernel, dim3((unsigned)((J + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, (const float*)part,
+              ntiles, (int)J, ntok, accum, avg_out);
+  if (rc != VT_OK) return rc;
+  return launch(fsq_aux_finish_kernel, dim3(1), dim3(1), 0, stream, (const float*)accum, ntok, ntok * (long long)D, out3);
 }

@@ -9,9 +9,7 @@
 // Layout: blockIdx.y = segment, blockIdx.x strides over the segment's bytes.  16-byte loads and stores where both ends are
 // 16-byte aligned, 4-byte where they are 4-byte aligned, bytes otherwise; the tail past the last whole vector is copied by
 // the threads of the segment's first block.
-#include <algorithm>
-
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -62,14 +60,10 @@ __global__ void __launch_bounds__(kBlock) copy_segments_kernel(const vt_copy_seg
 }  // namespace
 
 extern "C" int vt_copy_segments(const vt_copy_segment* table, int32_t n, int64_t max_bytes, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(n >= 0 && max_bytes >= 0, "vt_copy_segments: bad arguments");
   if (n == 0) return VT_OK;
   VT_CHECK_ARG(table != nullptr && n <= 65535, "vt_copy_segments: table must be a device array of 1 .. 65535 entries");
   // max_bytes only sizes the grid (each block strides over its segment, whatever its length)
-  const int64_t per = ceil_div64(std::max<int64_t>(max_bytes, 1), (int64_t)kBlock * 16 * kUnroll);
-  const int gx = (int)std::min<int64_t>(std::max<int64_t>(per, 1), kMaxBlocksPerSeg);
-  hipLaunchKernelGGL(copy_segments_kernel, dim3(gx, n), dim3(kBlock), 0, stream, table);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const dim3 grid(grid_for(max_bytes, (long long)kBlock * 16 * kUnroll, kMaxBlocksPerSeg), n);
+  return launch(copy_segments_kernel, grid, dim3(kBlock), 0, as_stream(stream_), table);
 }

@@ -8,7 +8,7 @@
 //   chain: copy frames between NCTHW tensors with optional clamp (--pad_gen_frames: the last f-1 generated frames are
 //          prepended to the next clip, inference_reconstruct.py:213-221)
 // All three are HBM-bound byte / fp32 streams: one thread per output element, coalesced along W.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -112,13 +112,6 @@ __global__ __launch_bounds__(kBlock) void ncthw_copy_frames_kernel(const float* 
   }
 }
 
-inline unsigned grid_for(long long n) {
-  long long b = (n + kBlock - 1) / kBlock;
-  if (b > 65536) b = 65536;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 inline AAxis make_axis(int in_size, int out_size) {
   AAxis a;
   a.in_size = in_size;
@@ -135,38 +128,30 @@ extern "C" int64_t vt_frames_work_floats(int32_t T, int32_t H0, int32_t W) { ret
 extern "C" int vt_frames_u8_to_ncthw(const uint8_t* frames, int32_t T, int32_t H0, int32_t W0, int32_t Hr, int32_t Wr, int32_t top,
                                      int32_t left, float* x, int32_t Tdst, int32_t t_off, int32_t H, int32_t W, float* work,
                                      vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = as_stream(stream_);
   VT_CHECK_ARG(frames && x && work, "vt_frames_u8_to_ncthw: null pointer");
   VT_CHECK_ARG(T > 0 && H0 > 0 && W0 > 0 && Hr > 0 && Wr > 0 && H > 0 && W > 0, "vt_frames_u8_to_ncthw: bad dims");
   VT_CHECK_ARG(top >= 0 && left >= 0 && top + H <= Hr && left + W <= Wr, "vt_frames_u8_to_ncthw: crop window outside the resized frame");
   VT_CHECK_ARG(t_off >= 0 && t_off + T <= Tdst, "vt_frames_u8_to_ncthw: frame range outside the destination");
-  hipLaunchKernelGGL(frames_resize_w_kernel, dim3(grid_for((long long)T * 3 * H0 * W)), dim3(kBlock), 0, stream, frames, work, T, H0,
-                     W0, W, left, make_axis(W0, Wr));
-  VT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(frames_resize_h_kernel, dim3(grid_for((long long)T * 3 * H * W)), dim3(kBlock), 0, stream, (const float*)work, x, T,
-                     H0, H, W, top, Tdst, t_off, make_axis(H0, Hr));
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  const int rc = launch(frames_resize_w_kernel, dim3(grid_for((long long)T * 3 * H0 * W, kBlock, 65536)), dim3(kBlock), 0, stream, frames, work, T, H0,
+                        W0, W, left, make_axis(W0, Wr));
+  if (rc != VT_OK) return rc;
+  return launch(frames_resize_h_kernel, dim3(grid_for((long long)T * 3 * H * W, kBlock, 65536)), dim3(kBlock), 0, stream, (const float*)work, x, T,
+                H0, H, W, top, Tdst, t_off, make_axis(H0, Hr));
 }
 
 extern "C" int vt_ncthw_to_frames_u8(const float* x, int32_t Tsrc, int32_t t0, int32_t n, int32_t H, int32_t W, uint8_t* out,
                                      int32_t Wtot, int32_t w_off, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(x && out && n > 0 && H > 0 && W > 0, "vt_ncthw_to_frames_u8: bad arguments");
   VT_CHECK_ARG(t0 >= 0 && t0 + n <= Tsrc && w_off >= 0 && w_off + W <= Wtot, "vt_ncthw_to_frames_u8: frame / column range");
-  hipLaunchKernelGGL(ncthw_to_frames_u8_kernel, dim3(grid_for((long long)n * H * W * 3)), dim3(kBlock), 0, stream, x, out, Tsrc, t0, n,
-                     H, W, Wtot, w_off);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(ncthw_to_frames_u8_kernel, dim3(grid_for((long long)n * H * W * 3, kBlock, 65536)), dim3(kBlock), 0, as_stream(stream_), x, out, Tsrc, t0, n,
+                H, W, Wtot, w_off);
 }
 
 extern "C" int vt_ncthw_copy_frames(const float* src, float* dst, int32_t C, int32_t Ts, int32_t Td, int32_t ts0, int32_t td0, int32_t n,
                                     int64_t HW, int32_t clamp, vt_stream stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   VT_CHECK_ARG(src && dst && C > 0 && n > 0 && HW > 0, "vt_ncthw_copy_frames: bad arguments");
   VT_CHECK_ARG(ts0 >= 0 && ts0 + n <= Ts && td0 >= 0 && td0 + n <= Td, "vt_ncthw_copy_frames: frame range");
-  hipLaunchKernelGGL(ncthw_copy_frames_kernel, dim3(grid_for((long long)C * n * HW)), dim3(kBlock), 0, stream, src, dst, C, Ts, Td, ts0,
-                     td0, n, (long long)HW, clamp);
-  VT_CHECK_LAUNCH();
-  return VT_OK;
+  return launch(ncthw_copy_frames_kernel, dim3(grid_for((long long)C * n * HW, kBlock, 65536)), dim3(kBlock), 0, as_stream(stream_), src, dst, C, Ts, Td, ts0,
+                td0, n, (long long)HW, clamp);
 }

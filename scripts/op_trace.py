@@ -129,12 +129,12 @@ def forward_case(name, dtype, **build):
     return run
 
 
-def tiled_case(name, overlap):
+def tiled_case(name, overlap, frames=17):
     def run():
         model = build_model(name, seed=3)[0]
         model.use_tiling, model.t_chunk_enc, model.t_chunk_dec, model.use_overlap = True, 8, 2, overlap
         torch.manual_seed(1)
-        model(smallest_clip(model, frames=17))          # chunks of 1, 8, 8 frames; 5 latent frames in chunks of 1, 2, 2
+        model(smallest_clip(model, frames=frames))      # 17 frames at f = 4: chunks of 1, 8, 8 frames; 5 latent frames in chunks of 1, 2, 2
     return run
 
 
@@ -178,6 +178,10 @@ def cases():
                                                 reg_overrides=dict(dim=8, levels=[8, 8, 8, 5, 5, 5]))))
     for overlap in (False, True):
         out.append((f"tiled {v11} overlap={overlap}", tiled_case(v11, overlap)))
+    # the other temporal factors under overlap (f = 2; f = 8, long enough for a later chunk to carry a look-ahead latent; 16x spatial)
+    for name, frames in (("vidtok_v1_1/vidtok_kl_causal_288_8chn_v1_1", 17), ("vidtok_v1_1/vidtok_fsq_causal_888_32768_v1_1", 33),
+                         ("vidtok_v1_1/vidtok_kl_causal_41616_16chn_v1_1", 17)):
+        out.append((f"tiled {name} overlap=True", tiled_case(name, True, frames)))
     out.append((f"sessions {v11}", session_case(v11)))
     for name in (v10, v11):
         for recompute in ("none", "norms", "stages"):

@@ -90,7 +90,7 @@ def main():
         s._restore()
 
     def switch_torch():                       # the same bytes as one torch copy per cache tensor, both ways
-        bufs = [m.causal_cache for m in s._mods]
+        bufs = [slot.cache for slot in s.state.slots]
         for sv, b in zip(s._saved, bufs):
             if sv is not None and b is not None:
                 b.copy_(sv)
@@ -99,7 +99,7 @@ def main():
                 sv.copy_(b)
 
     def switch_segments():                    # the device part of a switch alone: the two vt_copy_segments launches
-        bufs = [m.causal_cache for m in s._mods]
+        bufs = [slot.cache for slot in s.state.slots]
         s._copy([(sv, b) for sv, b in zip(s._saved, bufs) if sv is not None and b is not None])
         s._copy([(b, sv) for sv, b in zip(s._saved, bufs) if sv is not None and b is not None])
 
@@ -115,7 +115,7 @@ def main():
     out["switch"] = {"caches": n_caches, "cache_bytes": cache_bytes, "us_per_switch": round(t_sw * 1e6, 2),
                      "us_two_copy_segments": round(t_seg * 1e6, 2), "us_torch_copy_per_tensor": round(t_sw_torch * 1e6, 2),
                      "GBps_copy_segments": round(2 * 2 * cache_bytes / t_seg / 1e9, 1),
-                     "note": "us_per_switch: wall time of what a push adds (state in + out, snapshot / restore of the module attributes); "
+                     "note": "us_per_switch: wall time of what a push adds (state in + out, snapshot / restore of the chunk states); "
                              "the other two: the same 2 x cache_bytes moved as two vt_copy_segments launches vs one torch copy per tensor; "
                              "GBps counts bytes read + written"}
 

@@ -492,6 +492,29 @@ def test_tiled_chunks_replay_bit_exact(name, dtype, overlap):
     assert len([e for e in model._gdec.entries.values() if isinstance(e, tuple)]) >= 3
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+def test_overlap_switch_under_graphs_matches_fresh_model(dtype):
+    """Every tiled pass applies the overlapped cache offsets or zeros (vidtok_amd/chunks.py): two overlapped forwards, then two
+    without the look-ahead on the same graph-enabled model -- 25 frames = 7 latent frames, so the later-chunk kind occurs twice in a
+    pass and the second pass of each setting replays every chunk -- end on the bits of a fresh graph-enabled model that only ever ran
+    without overlap, and of the same sequence with graphs off."""
+    x = (torch.rand((1, 3, 25, 32, 32), generator=torch.Generator().manual_seed(31)) * 2 - 1).to(DEV)
+
+    def last_of(graphs, overlaps):
+        model = build_model("vidtok_v1_1/vidtok_kl_causal_488_4chn_v1_1", seed=14, device=DEV, dtype=dtype)[0]
+        model.regularization.sample = False
+        model.use_tiling, model.t_chunk_enc, model.t_chunk_dec = True, 8, 2
+        model.enable_graphs(graphs)
+        for overlap in overlaps:
+            model.use_overlap = overlap
+            dec = model(x)[1]
+        return dec
+
+    last = last_of(True, (True, True, False, False))
+    assert torch.equal(last, last_of(True, (False, False)))
+    assert torch.equal(last, last_of(False, (True, True, False, False)))
+
+
 @pytest.mark.parametrize("ov,T", [(dict(resamp_with_conv=False), 5), (dict(init_pad_mode="constant"), 6),
                                   (dict(init_pad_mode="reflect"), 6), (dict(tanh_out=True), 5), (dict(give_pre_end=True), 5)],
                          ids=["no_resamp_conv", "pad_constant", "pad_reflect", "tanh_out", "give_pre_end"])

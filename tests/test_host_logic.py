@@ -319,15 +319,18 @@ def test_rare_constructor_options_match_oracle(ov, T, emulated_ops):
 
 
 def test_chunk_cache_buffers_are_released_between_eager_passes(emulated_ops):
-    """ADVICE r2: the persistent v1.1 chunk-cache buffers (modules.py::_CausalState._persistent) must not accumulate:
+    """ADVICE r2: the persistent v1.1 chunk-cache buffers (chunks.py::Slot.persistent) must not accumulate:
     an eager tiled pass leaves one buffer per (module, shape), the next encode / decode starts by dropping them, and
     invalidate_graphs() / .to() drop them when the graph cache is on."""
     model, cfg, sd = build_model("vidtok_v1_1/vidtok_kl_causal_488_16chn_v1_1", seed=3)
     model.use_tiling, model.t_chunk_enc, model.use_overlap = True, 8, True
     model.t_chunk_dec = 2
 
+    def slots():
+        return [s for st in model._chunk_states() for s in st.slots]
+
     def n_bufs():
-        return sum(len(m.__dict__.get("_cache_bufs", {})) for m in model.modules())
+        return sum(len(s.bufs) for s in slots())
 
     x = torch.rand(1, 3, 17, 16, 16) * 2 - 1
     model(x)
@@ -336,7 +339,7 @@ def test_chunk_cache_buffers_are_released_between_eager_passes(emulated_ops):
     model(torch.rand(1, 3, 17, 16, 24) * 2 - 1)             # another resolution: the first one's buffers are gone
     assert n_bufs() <= per_pass
     model._empty_causal_cached(model)
-    assert n_bufs() == 0 and all(getattr(m, "causal_cache", None) is None for m in model.modules())
+    assert n_bufs() == 0 and all(s.cache is None for s in slots())
     model.use_graphs = True                                   # (no capture on the host; only the bookkeeping is tested)
     model(x)
     model._empty_causal_cached(model.encoder)
@@ -345,9 +348,10 @@ def test_chunk_cache_buffers_are_released_between_eager_passes(emulated_ops):
     assert n_bufs() == 0                                      # ... until the graphs go
 
 
-def test_graph_cache_bookkeeping_and_engine_copies():
+def test_graph_cache_bookkeeping_and_engine_copies(emulated_ops):
     """GraphedCall keeps at most MAX_ENTRIES shapes (LRU; stateful chunk graphs are only dropped by the owner between
-    passes), and a deep copy / pickle of an engine runs ITS OWN encoder and decoder (closures over `self`)."""
+    passes), and a deep copy / pickle of an engine runs ITS OWN encoder and decoder (closures over `self`) on
+    its own chunk state: a tiled pass on the copy binds no cache on the original."""
     import copy
     import pickle
 
@@ -379,6 +383,17 @@ def test_graph_cache_bookkeeping_and_engine_copies():
         assert other.decoder.conv_in.site.conv is other.decoder.conv_in.conv and blk.sites[0].conv is blk.conv1
         assert up.fold_site.conv is up.conv and all(s.conv is up.conv for _py, _px, s in up.parity_sites)
         assert list(other.state_dict()) == list(model.state_dict())
+
+    model = build_model("vidtok_v1_1/vidtok_kl_causal_488_4chn_v1_1", seed=3)[0]
+    for other in (copy.deepcopy(model), pickle.loads(pickle.dumps(model))):
+        assert other.encoder.chunks.slots[0] is other.encoder.conv_in.slot and other.encoder.conv_in.slot.state is other.encoder.chunks
+        assert other._gdec.state_get.__self__ is other and list(other.state_dict()) == list(model.state_dict())
+        other.use_tiling, other.t_chunk_enc, other.t_chunk_dec = True, 8, 2
+        other(torch.rand(1, 3, 9, 16, 16) * 2 - 1)
+        for st in other._chunk_states():
+            assert any(s.cache is not None for s in st.slots)
+        for st in model._chunk_states():
+            assert all(s.cache is None and not s.bufs for s in st.slots)
 
 
 def test_autocast_region_switches_the_arithmetic_mode():

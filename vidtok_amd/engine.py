@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, packing
+from .chunks import ChunkState
 from .config import instantiate_from_config
 from .graphs import GraphedCall
 
@@ -57,8 +58,8 @@ class AutoencodingEngine(nn.Module):
             raise NotImplementedError("temporal tiling exists only in the v1.1 models of the reference")
         self.use_graphs = False
         # bound methods, not closures: copy.deepcopy / pickle of the engine then rebind them to the copy
-        self._genc = GraphedCall(self._encoder_fn, self._encoder_state, self._set_chunk_state, self._encoder_version)
-        self._gdec = GraphedCall(self._decoder_fn, self._decoder_state, self._set_chunk_state, self._decoder_version)
+        self._genc = GraphedCall(self._encoder_fn, self._encoder_state, ChunkState.bind, self._encoder_version)
+        self._gdec = GraphedCall(self._decoder_fn, self._decoder_state, ChunkState.bind, self._decoder_version)
         if verbose:
             _print0(f"[vidtok_amd.engine][AutoencodingEngine] Use ckpt_path: {ckpt_path}")
         if ckpt_path is not None:
@@ -160,19 +161,16 @@ class AutoencodingEngine(nn.Module):
 
     def invalidate_graphs(self):
         """forget captured graphs (call after editing parameters in place) and the v1.1 chunk-cache buffers they replay
-        against (vidtok_amd/modules.py::_CausalState._persistent)"""
+        against (vidtok_amd/chunks.py::Slot.persistent)"""
         self._genc.clear()
         self._gdec.clear()
         self.__dict__.pop("_graph_params", None)
-        self._drop_cache_buffers(self)
+        for st in self._chunk_states():
+            st.reset(drop_buffers=True)
 
-    @staticmethod
-    def _drop_cache_buffers(root):
-        for m in root.modules():
-            if "_cache_bufs" in m.__dict__:
-                m.__dict__["_cache_bufs"].clear()
-                if hasattr(m, "causal_cache"):
-                    m.causal_cache = None
+    def _chunk_states(self):
+        """the chunk state of each half that has one (vidtok_amd/chunks.py; the non-causal family has none)"""
+        return [p.chunks for p in (self.encoder, self.decoder) if hasattr(p, "chunks")]
 
     def _encoder_fn(self, t):
         return self.encoder(t)
@@ -197,10 +195,10 @@ class AutoencodingEngine(nn.Module):
         return self._params_version("decoder")
 
     def _encoder_state(self):
-        return self._chunk_state(self.encoder)
+        return self.encoder.chunks.caches()
 
     def _decoder_state(self):
-        return self._chunk_state(self.decoder)
+        return self.decoder.chunks.caches()
 
     def _apply(self, fn, *a, **kw):           # .to() / .cuda() / .float(): parameters move, captured graphs are stale
         self.invalidate_graphs()
@@ -209,16 +207,6 @@ class AutoencodingEngine(nn.Module):
     def load_state_dict(self, *a, **kw):
         self.invalidate_graphs()
         return super().load_state_dict(*a, **kw)
-
-    @staticmethod
-    def _chunk_state(root):
-        """[(module, its chunk-to-chunk cache)] of a sub-tree (v1.1 tiling; empty for v1.0 models)"""
-        return [(m, m.causal_cache) for m in root.modules() if hasattr(m, "causal_cache")]
-
-    @staticmethod
-    def _set_chunk_state(state):
-        for m, c in state:
-            m.causal_cache = c
 
     def _run_encoder(self, x):
         key = (self.encoder.compute_dtype, getattr(self, "arith", None), getattr(self.encoder, "tail_dtype", None), getattr(self.encoder, "tail_level", None))
@@ -332,37 +320,26 @@ class AutoencodingEngineV11(AutoencodingEngine):
 
     version = "v1_1"
 
-    # -- cache / chunk protocol: walks the module tree exactly like the reference (:202-216) ------
+    # -- cache / chunk protocol of the reference (:202-216), as assignments on the two halves' states (vidtok_amd/chunks.py) ------
     def _empty_causal_cached(self, parent):
-        for _, module in parent.named_modules():
-            if hasattr(module, "causal_cache"):
-                module.causal_cache = None
-        if not self.use_graphs:
-            # eager passes own no captured addresses: the chunk-cache buffers go back to the allocator between clips, as
-            # the reference's caches do
-            self._drop_cache_buffers(parent)
-        elif self._genc.overfull or self._gdec.overfull:
+        # eager passes own no captured addresses: the chunk-cache buffers go back to the allocator between clips, as the
+        # reference's caches do
+        for st in (self._chunk_states() if parent is self else [parent.chunks]):
+            st.reset(drop_buffers=not self.use_graphs)
+        if self.use_graphs and (self._genc.overfull or self._gdec.overfull):
             # captured chunks replay against those buffers, so they live as long as the graphs: a process that keeps
             # meeting new chunk kinds (clip lengths, resolutions) starts over here, between two passes
             self.invalidate_graphs()
 
     def _set_first_chunk(self, is_first_chunk=True):
-        for module in self.modules():
-            if hasattr(module, "is_first_chunk"):
-                module.is_first_chunk = is_first_chunk
+        for st in self._chunk_states():
+            st.first = is_first_chunk
 
     def _set_fused_temporal(self):
         """Un-tiled passes never read the chunk caches, so blocks that can run as one fused launch (which keeps their
         convolutions' inputs on chip and therefore cannot leave caches behind) may do so; tiled passes may not."""
-        for module in self.modules():
-            if hasattr(module, "allow_fused"):
-                module.allow_fused = not self.use_tiling
-
-    def _set_cache_offset(self, modules, cache_offset=0):
-        for module in modules:
-            for submodule in module.modules():
-                if hasattr(submodule, "cache_offset"):
-                    submodule.cache_offset = cache_offset
+        for st in self._chunk_states():
+            st.tiled = self.use_tiling
 
     def build_chunk_start_end(self, t, decoder_mode=False):
         """[[0,1],[1,1+c],[1+c,1+2c],...]: the first chunk is the single leading frame (:218-228)."""
@@ -405,9 +382,8 @@ class AutoencodingEngineV11(AutoencodingEngine):
         after the single-frame first one meets shorter caches than the ones after it)."""
         if not (self.use_graphs and x.is_cuda):
             return module(self._chunk_of(x, start, end))
-        sig = tuple(0 if c is None else c.shape[1] for _, c in self._chunk_state(module))
         key = (module.compute_dtype, getattr(self, "arith", None), getattr(module, "tail_dtype", None), getattr(module, "tail_level", None),
-               "chunk", bool(first), bool(self.use_overlap), sig)
+               "chunk", bool(first), module.chunks.overlap, module.chunks.sig())
         return graphed(x, key, stateful=True, frames=(start, end), borrow=True)
 
     def tile_encode(self, x: Any) -> Any:
@@ -455,33 +431,17 @@ class AutoencodingEngineV11(AutoencodingEngine):
         self._empty_causal_cached(self.decoder)
         self._set_first_chunk(True)
         self._set_fused_temporal()
+        # the overlapped offsets or zeros, every pass (a pass does not inherit the previous one's)
+        self.decoder.chunks.set_overlap(self.use_tiling and self.use_overlap)
         if self.use_tiling:
             return self.tile_decode(z)
         return self._run_decoder(z)
-
-    def _overlap_offsets(self):
-        """cache_offset per decoder sub-tree when chunks carry one look-ahead latent frame: 1 at latent
-        rate, doubling after each temporal up-sampler (autoencoder_v1_1.py:307-320)."""
-        f, d = self.encoder.time_downsample_factor, self.decoder
-        assert f in [2, 4, 8], "Only support 2x, 4x or 8x temporal downsampling now."
-        self._set_cache_offset([d], 1)
-        if f == 4:
-            self._set_cache_offset([d.up_temporal[2].upsample, d.up_temporal[1]], 2)
-            self._set_cache_offset([d.up_temporal[1].upsample, d.up_temporal[0], d.conv_out], 4)
-        elif f == 2:
-            self._set_cache_offset([d.up_temporal[2].upsample, d.up_temporal[1], d.up_temporal[0], d.conv_out], 2)
-        else:
-            self._set_cache_offset([d.up_temporal[3].upsample, d.up_temporal[2]], 2)
-            self._set_cache_offset([d.up_temporal[2].upsample, d.up_temporal[1]], 4)
-            self._set_cache_offset([d.up_temporal[1].upsample, d.up_temporal[0], d.conv_out], 8)
 
     def tile_decode(self, z: Any) -> torch.Tensor:
         """chunks decoded in order, each with one look-ahead latent frame when `use_overlap` (its f trailing output
         frames are dropped); outputs land in one preallocated tensor (autoencoder_v1_1.py:302-331)"""
         num_frames = z.shape[2]
         f = self.encoder.time_downsample_factor
-        if self.use_overlap:
-            self._overlap_offsets()
         chunks = self.build_chunk_start_end(num_frames, decoder_mode=True)
         out, done = None, 0
         for idx, (start, end) in enumerate(chunks):

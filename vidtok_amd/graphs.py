@@ -16,7 +16,7 @@ need `invalidate_graphs()`.  A call site keeps at most `GraphedCall.MAX_ENTRIES`
 graphs share one memory pool, so a process that sees many clip lengths / resolutions does not accumulate working sets.
 
 Stateful chunked passes (v1.1 temporal tiling) replay too: the modules keep their chunk-to-chunk caches in persistent
-buffers that are updated in place (vidtok_amd/modules.py::_CausalState), so a captured chunk reads and writes the same
+buffers that are updated in place (vidtok_amd/chunks.py::Slot.persistent), so a captured chunk reads and writes the same
 addresses on every replay.  Such a call (`stateful=True`) must run exactly once per chunk: the usual side-stream warm-up
 run before the capture is skipped (the first, eager call of the shape already packed the weights), and capturing does
 not execute.  `frames=(start, end)` passes the chunk as a frame range of a larger NCTHW fp32 tensor (copied straight

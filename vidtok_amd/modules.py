@@ -11,8 +11,8 @@ containers (initialisation + key names); their forward() is never called.
 
 `version` selects the reference variant: "v1_0" = zero causal padding, nearest time up-sampling,
 decoder drops 3 frames; "v1_1" = first-frame-replicate / cached causal padding, trilinear time
-up-sampling, chunk-to-chunk caches (`causal_cache`, `is_first_chunk`, `cache_offset` attributes
-exactly as model_3dcausal_v1_1.py:155-157,212-214 so an engine can drive them).
+up-sampling, chunk-to-chunk caches (model_3dcausal_v1_1.py:155-157,212-214: every caching module reads
+its `slot`, the encoder / decoder owns the `chunks` state an engine drives; vidtok_amd/chunks.py).
 """
 import dataclasses
 import functools
@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import lib as L
 from . import ops
+from .chunks import ChunkState, Slot, slots_of
 from .ops import ConvGeom
 from .packing import (ConvSite, space_upsample_parity_mix, space_upsample_parity_weights, time_upsample3_mix, time_upsample3_weights,
                       time_upsample_parity_mix, time_upsample_parity_weights)
@@ -131,18 +132,8 @@ def Normalize(in_channels, norm_type="layernorm"):
     return GroupNorm32(in_channels) if norm_type == "groupnorm" else LayerNorm(in_channels, eps=1e-6)
 
 
-def _persistent_cache(module, shape, like):
-    """see _CausalState._persistent (the time resamplers carry a cache without being causal convolutions)"""
-    return _CausalState._persistent(module, shape, like)
-
-
 class _CausalState:
-    """v1.1 chunk-to-chunk state shared by the causal convs (model_3dcausal_v1_1.py:155-178)."""
-
-    def _init_state(self):
-        self.is_first_chunk = True
-        self.causal_cache = None
-        self.cache_offset = 0
+    """v1.1 chunk-to-chunk behaviour shared by the causal convs (model_3dcausal_v1_1.py:155-178); the state is `self.slot`."""
 
     def _clip_tmode(self):
         """the time-pad mode on a whole clip (= the first chunk)"""
@@ -159,32 +150,20 @@ class _CausalState:
     def _tmode_and_cache(self, version, time_pad):
         if version == "v1_0" or time_pad == 0:
             return L.VT_TPAD_ZERO, None
-        if self.is_first_chunk:
+        if self.slot.first:
             return L.VT_TPAD_REPLICATE, None
-        if self.causal_cache is None or self.causal_cache.shape[1] < time_pad:
-            raise RuntimeError("causal cache missing: run the first chunk with is_first_chunk=True")
-        return L.VT_TPAD_CACHE, self.causal_cache
-
-    def _persistent(self, shape, like):
-        """The cache lives in one buffer per (module, shape), allocated on first use and rewritten in place afterwards:
-        a chunk of a given kind reads and writes the same addresses every time, which is what lets a captured chunk
-        (vidtok_amd/graphs.py) be replayed.  `causal_cache` (the reference's attribute, reset to None between clips) is
-        bound to the buffer after each update; `_cache_bufs` survives the reset."""
-        if "_cache_bufs" not in self.__dict__:
-            self._cache_bufs = {}
-        bufs = self._cache_bufs
-        key = (tuple(shape), like.dtype, like.device)
-        buf = bufs.get(key)
-        if buf is None:
-            buf = bufs[key] = torch.empty(tuple(shape), dtype=like.dtype, device=like.device)
-        return buf
+        cache = self.slot.cache
+        if cache is None or cache.shape[1] < time_pad:
+            raise RuntimeError("causal cache missing: run the first chunk first")
+        return L.VT_TPAD_CACHE, cache
 
     def _update_cache(self, x, time_pad):
-        """Keep the last `time_pad` frames of padded[:len-cache_offset] where
+        """Keep the last `time_pad` frames of padded[:len-offset] where
         padded = [pad frames (x[0] repeated | previous cache), x]  (model_3dcausal_v1_1.py:172-176)."""
         if time_pad == 0:
             return
-        T, off, P = x.shape[1], self.cache_offset, time_pad
+        slot = self.slot
+        T, off, P = x.shape[1], slot.offset, time_pad
         src_x, src_c = [], []  # (dst slot, frame index)
         for j in range(P):
             q = T - off + j            # index into the padded sequence
@@ -192,20 +171,20 @@ class _CausalState:
                 src_x.append((j, q - P))
             elif q < 0:
                 raise RuntimeError("chunk shorter than cache_offset")
-            elif self.is_first_chunk:
+            elif slot.first:
                 src_x.append((j, 0))
             else:
                 src_c.append((j, q))
         # slots taken from the old cache come first (q grows with j), the ones from x after them.  The old frames move
         # inside the buffer they are read from: through a temporary (launches are stream-ordered, so the buffer is
         # rewritten only after the copy -- and after the convolution that read it -- has finished)
-        kept = ops.gather_frames(self.causal_cache, [i for _, i in src_c]) if src_c else None
-        buf = self._persistent((x.shape[0], P) + tuple(x.shape[2:]), x)
+        kept = ops.gather_frames(slot.cache, [i for _, i in src_c]) if src_c else None
+        buf = slot.persistent((x.shape[0], P) + tuple(x.shape[2:]), x)
         if kept is not None:
             ops.gather_frames(kept, list(range(len(src_c))), out=buf, out_t0=src_c[0][0])
         if src_x:
             ops.gather_frames(x, [i for _, i in src_x], out=buf, out_t0=src_x[0][0])
-        self.causal_cache = buf
+        slot.cache = buf
 
 
 class CausalConv3d(nn.Module, _CausalState):
@@ -222,7 +201,7 @@ class CausalConv3d(nn.Module, _CausalState):
         self.chan_out = chan_out
         self.version = version
         self.site = ConvSite(self.conv, self.geom(), clip_tmode=self._clip_tmode())
-        self._init_state()
+        self.slot = Slot()
 
     def geom(self, ups_t=0):
         kt, kh, kw = self.ks
@@ -243,7 +222,7 @@ class CausalConv1d(nn.Module, _CausalState):
         self.chan_out = chan_out
         self.version = version
         self.site = ConvSite(self.conv, ConvGeom(kt=self.k, st=self.stride, pt=self.time_pad), clip_tmode=self._clip_tmode())
-        self._init_state()
+        self.slot = Slot()
 
 
 _G3x3 = ConvGeom(kh=3, kw=3, ph=1, pw=1, ph_hi=1, pw_hi=1)
@@ -327,19 +306,19 @@ class TimeDownsampleResCausal2x(nn.Module):
         self.conv = CausalConv3d(in_channels, out_channels, 3, stride=(2, 1, 1), version=version)
         self.mix_factor = nn.Parameter(torch.Tensor([mix_factor]))
         self.version = version
-        self.is_first_chunk = True
-        self.causal_cache = None
+        self.slot = Slot()
 
     def run(self, x, dt, next_norm=None):
         x = plain(x)
+        slot = self.slot
         if self.version == "v1_0":
             x1 = ops.time_avgpool3s2(x, L.VT_TPAD_ZERO)
         else:
-            if self.is_first_chunk:
+            if slot.first:
                 x1 = ops.time_avgpool3s2(x, L.VT_TPAD_REPLICATE)
             else:
-                x1 = ops.time_avgpool3s2(x, L.VT_TPAD_CACHE, cache=self.causal_cache)
-            self.causal_cache = ops.gather_frames(x, [x.shape[1] - 1], out=_persistent_cache(self, (x.shape[0], 1) + tuple(x.shape[2:]), x))
+                x1 = ops.time_avgpool3s2(x, L.VT_TPAD_CACHE, cache=slot.cache)
+            slot.cache = ops.gather_frames(x, [x.shape[1] - 1], out=slot.persistent((x.shape[0], 1) + tuple(x.shape[2:]), x))
         return _wrap(self.conv.run(x, dt, res=x1, res_mode=L.VT_RES_MIX, mix_factor=self.mix_factor.detach(),
                                    **_emit(next_norm)), next_norm)
 
@@ -397,8 +376,7 @@ class TimeUpsampleResCausal2x(nn.Module):
         self.num_temp_upsample = num_temp_upsample
         self.enable_cached = interpolation_mode == "trilinear"
         self.version = version
-        self.is_first_chunk = True
-        self.causal_cache = None
+        self.slot = Slot()
         # v1.0, up(x)[t] = x[t >> 1]: the 3 temporal taps of an output frame hit 2 input frames, so even / odd output frames are two
         # k=2 causal convs over x with pre-summed weights (2/3 of the MACs of the 27-tap form):
         #   o[2j] = (W0+W1) x[j-1] + W2 x[j]      o[2j+1] = W0 x[j-1] + (W1+W2) x[j]
@@ -413,28 +391,29 @@ class TimeUpsampleResCausal2x(nn.Module):
                                     mix=functools.partial(time_upsample3_mix, part="v")))
 
     def _interp_v11(self, x):
-        n, T = self.num_temp_upsample, x.shape[1]
+        n, T, slot = self.num_temp_upsample, x.shape[1], self.slot
         if not self.enable_cached:
             return ops.gather_frames(x, [t // 2 for t in range(2 * T)])
-        if not self.is_first_chunk:
-            nc = self.causal_cache.shape[1]
+
+        def keep_frames(src, keep):
+            slot.cache = ops.gather_frames(src, keep, out=slot.persistent((x.shape[0], len(keep)) + tuple(x.shape[2:]), x))
+
+        if not slot.first:
+            nc = slot.cache.shape[1]
             Tc = nc + T
             if Tc - 2 * n >= nc:
                 # the frames to keep all lie in x: [cache | x] is never assembled -- the interpolation reads both parts in
                 # place and leaves out the frames the previous chunk delivered; then the cache buffer is rewritten
-                up = ops.time_lerp2x_cat(self.causal_cache, x, 2 * n)
-                keep = list(range(Tc - 2 * n - nc, Tc - n - nc))
-                self.causal_cache = ops.gather_frames(x, keep, out=_persistent_cache(self, (x.shape[0], len(keep)) + tuple(x.shape[2:]), x))
+                up = ops.time_lerp2x_cat(slot.cache, x, 2 * n)
+                keep_frames(x, list(range(Tc - 2 * n - nc, Tc - n - nc)))
                 return up
             xc = torch.empty((x.shape[0], Tc) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)   # [cache | x]
-            ops.gather_frames(self.causal_cache, list(range(nc)), out=xc, out_t0=0)
+            ops.gather_frames(slot.cache, list(range(nc)), out=xc, out_t0=0)
             ops.gather_frames(x, list(range(T)), out=xc, out_t0=nc)
-            keep = list(range(max(0, Tc - 2 * n), Tc - n))       # (xc is a copy: the cache buffer is free to be rewritten)
-            self.causal_cache = ops.gather_frames(xc, keep, out=_persistent_cache(self, (x.shape[0], len(keep)) + tuple(x.shape[2:]), x))
+            keep_frames(xc, list(range(max(0, Tc - 2 * n), Tc - n)))       # (xc is a copy: the cache buffer is free to be rewritten)
             up = ops.time_lerp2x(xc)
             return ops.gather_frames(up, list(range(2 * n, 2 * Tc)))
-        keep = list(range(max(0, T - n), T))
-        self.causal_cache = ops.gather_frames(x, keep, out=_persistent_cache(self, (x.shape[0], len(keep)) + tuple(x.shape[2:]), x))
+        keep_frames(x, list(range(max(0, T - n), T)))
         hn = min(n, T)
         up = torch.empty((x.shape[0], 2 * T) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
         ops.time_lerp2x(ops.gather_frames(x, list(range(0, hn))), out=up, out_t0=0)              # head: its own interpolation
@@ -542,11 +521,9 @@ class ResnetCausalBlock1D(nn.Module):
             self.conv2.conv.weight.data.zero_()
             self.conv2.conv.bias.data.zero_()
 
-    # v1.1 blocks keep chunk-to-chunk caches of their convolutions' INPUTS, which a fused launch never materialises.  An
-    # engine that is NOT tiling sets `allow_fused` (AutoencodingEngineV11._set_fused_temporal): no chunk follows, nothing
-    # to keep.  A tiling engine leaves it False and the launch keeps the chunk state itself (ops.temporal_block `caches`);
-    # v1.0 has no caches.
-    allow_fused = False
+    # v1.1 blocks keep chunk-to-chunk caches of their convolutions' INPUTS, which a fused launch never materialises.  In a
+    # pass that is NOT tiled (AutoencodingEngineV11._set_fused_temporal) no chunk follows and there is nothing to keep; in
+    # a tiled one the launch keeps the chunk state itself (ops.temporal_block `caches`); v1.0 has no caches.
 
     def _fusable(self, dt):
         """may run as ONE launch (ops.temporal_block): LayerNorm variant, C -> C, bf16"""
@@ -556,28 +533,28 @@ class ResnetCausalBlock1D(nn.Module):
             return False
         if self.in_channels != 128:          # the kernel's LayerNorm statistics span exactly 128 REAL channels
             return False
-        if self.conv1.version == "v1_0" or (self.allow_fused and self.conv1.is_first_chunk):
+        s1, s2 = self.conv1.slot, self.conv2.slot
+        if self.conv1.version == "v1_0" or (s1.first and not s1.tiled):
             return True
         # a chunk of a tiled v1.1 pass: both convolutions at the same point of the chunk schedule, and -- past the first
         # chunk -- both caches there
-        c1, c2 = self.conv1, self.conv2
-        if c1.cache_offset != c2.cache_offset or c1.is_first_chunk != c2.is_first_chunk:
+        if s1.offset != s2.offset or s1.state is not s2.state:
             return False
-        return c1.is_first_chunk or (c1.causal_cache is not None and c2.causal_cache is not None)
+        return s1.first or (s1.cache is not None and s2.cache is not None)
 
     def _chunk_state(self, xp):
         """(tmode, caches, cache_offset) of a fused launch: (zero | replicate, None, 0) where no chunk state lives, else the
-        two persistent cache buffers (allocated on the first chunk, the convolutions' `causal_cache` afterwards)"""
-        c1, c2 = self.conv1, self.conv2
-        if c1.version == "v1_0":
+        two persistent cache buffers (allocated on the first chunk, the convolutions' caches afterwards)"""
+        s1, s2 = self.conv1.slot, self.conv2.slot
+        if self.conv1.version == "v1_0":
             return L.VT_TPAD_ZERO, None, 0
-        if self.allow_fused and c1.is_first_chunk:
+        if s1.first and not s1.tiled:
             return L.VT_TPAD_REPLICATE, None, 0
         shape = (xp.shape[0], 2) + tuple(xp.shape[2:])
-        if c1.is_first_chunk:
-            return L.VT_TPAD_REPLICATE, (c1._persistent(shape, xp), c2._persistent(shape, xp)), c1.cache_offset
-        ok = all(t.shape == shape and t.dtype == xp.dtype and t.is_contiguous() for t in (c1.causal_cache, c2.causal_cache))
-        return L.VT_TPAD_CACHE, ((c1.causal_cache, c2.causal_cache) if ok else None), c1.cache_offset
+        if s1.first:
+            return L.VT_TPAD_REPLICATE, (s1.persistent(shape, xp), s2.persistent(shape, xp)), s1.offset
+        ok = all(t.shape == shape and t.dtype == xp.dtype and t.is_contiguous() for t in (s1.cache, s2.cache))
+        return L.VT_TPAD_CACHE, ((s1.cache, s2.cache) if ok else None), s1.offset
 
     def first_norm(self, dt=None):
         # a fused block normalises x itself: its producer must not spend a write on LayerNorm1(x).  Whether the block then
@@ -602,7 +579,7 @@ class ResnetCausalBlock1D(nn.Module):
             out = ops.temporal_block(xp, w1, b1, w2, b2, self.norm1.affine(), self.norm2.affine(), tmode=tmode,
                                      eps=self.norm1.norm.eps, next_ln=nxt, keep_y=True, caches=caches, cache_offset=off)
             if caches is not None:          # the launch has rewritten the chunk state in place
-                self.conv1.causal_cache, self.conv2.causal_cache = caches
+                self.conv1.slot.cache, self.conv2.slot.cache = caches
             return out if nxt is None else Normed(out[0], out[1], next_norm[0], next_norm[1])
         return residual_block(self, SITE_POS, _causal_convs(self), x, dt, next_norm)
 
@@ -743,6 +720,7 @@ class EncoderCausal3DPadding(nn.Module):
         if self.fix_encoder:
             for p in self.parameters():
                 p.requires_grad = False
+        self.chunks = ChunkState(self)
 
     def _front_pad(self, T):
         f = self.time_downsample_factor
@@ -851,12 +829,26 @@ class DecoderCausal3DPadding(nn.Module):
         if self.fix_decoder:
             for p in self.parameters():
                 p.requires_grad = False
+        self.chunks = ChunkState(self)
+        self.chunks.overlap_table = self._overlap_table()
+
+    def _overlap_table(self):
+        """offset per slot when chunks carry one look-ahead latent frame: 1 at latent rate, doubling after each temporal
+        up-sampler (autoencoder_v1_1.py:307-320, which knows f = 2, 4, 8 and refuses the rest: None)"""
+        if self.time_downsample_factor not in (2, 4, 8):
+            return None
+        off, at = 1, {}
+        for stage in self.train_stage_modules() + [self.conv_out]:
+            if isinstance(stage, TimeUpsampleResCausal2x):
+                off *= 2
+            at.update((s, off) for s in slots_of(stage))
+        return [at.get(s, 1) for s in self.chunks.slots]
 
     def get_last_layer(self, **kwargs):
         return self.conv_out.conv.weight
 
     def train_stage_modules(self):
-        """the blocks between conv_in and norm_out in execution order (vidtok_amd/backward.py)"""
+        """the blocks between conv_in and norm_out in execution order"""
         stages = [self.mid.block_1, self.mid.attn_1, self.mid.block_2]
         for i_level in reversed(range(self.num_resolutions)):
             for i_block in range(self.num_res_blocks + 1):
@@ -880,14 +872,7 @@ class DecoderCausal3DPadding(nn.Module):
     def forward(self, z):
         dt = self.compute_dtype
         h = ops.ncthw_to_ndhwc(z.contiguous().float(), dt)
-        stages = [self.mid.block_1, self.mid.attn_1, self.mid.block_2]
-        for i_level in reversed(range(self.num_resolutions)):
-            for i_block in range(self.num_res_blocks + 1):
-                stages += [self.up[i_level].block[i_block], self.up_temporal[i_level].block[i_block]]
-            if i_level in self.spatial_us:
-                stages.append(self.up[i_level].upsample)
-                if i_level in self.tempo_us:
-                    stages.append(self.up_temporal[i_level].upsample)
+        stages = self.train_stage_modules()
         h = run_stages(stages, self.conv_in.run(h, dt, **_emit(first_norm_of(stages[0], dt))), dt,
                        last_norm=(self.norm_out, True), first=first_norm_of(stages[0], dt))
         trim = self.time_padding if self.version == "v1_0" else 0

@@ -13,16 +13,15 @@ order -- the generator is consumed as tile_encode consumes it).  A decode sessio
 it has arrived (tile_decode's `look` rule), or at finish.  A ReconstructSession chains both and reports at finish how many
 leading frames forward() drops.
 
-Each session owns its causal state.  Captured chunk graphs (engine.enable_graphs) replay against the modules' persistent cache
-buffers (modules.py::_CausalState._persistent), so a push copies the session's state into those buffers and back out afterwards
--- two vt_copy_segments launches whatever the number of caches -- and puts every module attribute it touched back: sessions,
+Each session owns its causal state.  Captured chunk graphs (engine.enable_graphs) replay against the slots' persistent cache
+buffers (chunks.py::Slot.persistent), so a push copies the session's state into those buffers and back out afterwards
+-- two vt_copy_segments launches whatever the number of caches -- and restores the snapshot of both halves' chunk states: sessions,
 interleaved with each other and with plain model(x) / encode / decode calls, do not see each other.  Device memory is bounded by
 the chunk (the frames of the incomplete chunk, the caches), not by the length of the video.
 """
 import torch
 
 from . import ops
-from .modules import _CausalState
 
 
 class ChunkSchedule:
@@ -99,11 +98,8 @@ class _Session:
         self.model, self.part = model, part
         self.f = model.encoder.time_downsample_factor
         self.sched = ChunkSchedule(step, lookahead)
-        self._mods = [m for m in part.modules() if hasattr(m, "causal_cache")]
-        # every module whose chunk attributes a push sets (the whole model: _set_first_chunk walks both halves)
-        self._touched = [m for m in model.modules() if hasattr(m, "causal_cache") or hasattr(m, "is_first_chunk") or hasattr(m, "allow_fused")]
-        self._fusable = [m for m in self._touched if hasattr(m, "allow_fused")]
-        self._saved = [None] * len(self._mods)
+        self.state = part.chunks
+        self._saved = [None] * len(self.state.slots)
         self._tables = {}
         self._pend = None
         self._geom = None           # (B, C, H, W) of the first push
@@ -145,27 +141,24 @@ class _Session:
 
     # ---- the switch --------------------------------------------------------------------------------------------------------
     def _enter(self):
-        m = self.model
-        self._snap = [(mod, mod.__dict__.get("causal_cache"), mod.__dict__.get("is_first_chunk"), mod.__dict__.get("cache_offset"),
-                       mod.__dict__.get("allow_fused", _ABSENT)) for mod in self._touched]
-        self._snap_overlap = m.use_overlap
-        for mod in self._fusable:
-            mod.allow_fused = False               # a tiled pass: blocks keep their chunk state (AutoencodingEngineV11._set_fused_temporal)
+        self._snap = [st.snapshot() for st in self.model._chunk_states()]     # both halves: _set_first_chunk writes both
+        self.state.set_overlap(self.sched.lookahead > 0)      # the decoder's cache offsets of an overlapped pass, else zeros
+        self.state.tiled = True                               # blocks keep their chunk state (AutoencodingEngineV11._set_fused_temporal)
         pairs = []
-        for mod, saved in zip(self._mods, self._saved):
+        for slot, saved in zip(self.state.slots, self._saved):
             if saved is None:
-                mod.causal_cache = None
+                slot.cache = None
                 continue
-            buf = _CausalState._persistent(mod, saved.shape, saved)
+            buf = slot.persistent(saved.shape, saved)
             pairs.append((saved, buf))
-            mod.causal_cache = buf
+            slot.cache = buf
         self._copy(pairs)
         self.switches += 1
 
     def _leave(self):
         pairs = []
-        for i, mod in enumerate(self._mods):
-            c = mod.causal_cache
+        for i, slot in enumerate(self.state.slots):
+            c = slot.cache
             if c is None:
                 self._saved[i] = None
                 continue
@@ -176,20 +169,9 @@ class _Session:
         self._copy(pairs)
 
     def _restore(self):
-        m = self.model
-        for mod, cache, first, off, fused in self._snap:
-            for k, v in (("causal_cache", cache), ("is_first_chunk", first), ("cache_offset", off)):
-                if v is not None or k in mod.__dict__:
-                    mod.__dict__[k] = v
-            if fused is _ABSENT:
-                mod.__dict__.pop("allow_fused", None)
-            else:
-                mod.allow_fused = fused
-        m.use_overlap = self._snap_overlap
+        for st, snap in zip(self.model._chunk_states(), self._snap):
+            st.restore(snap)
         self._snap = None
-
-    def _setup_part(self):
-        """per-session module settings for the length of a push (decode: the cache offsets of an overlapped pass)"""
 
     # ---- one push --------------------------------------------------------------------------------------------------------
     def _advance(self, n, fill, direct=None):
@@ -205,7 +187,6 @@ class _Session:
         if chunks:
             self._enter()
             try:
-                self._setup_part()
                 for s, e, look in chunks:
                     hi = e + (1 if look else 0)
                     if direct is not None and s >= base:
@@ -234,9 +215,6 @@ class _Session:
     @property
     def finished(self):
         return self.sched.finished
-
-
-_ABSENT = object()
 
 
 class EncodeSession(_Session):
@@ -358,14 +336,6 @@ class DecodeSession(_Session):
     def _alloc_pending(self):
         B, C, H, W = self._geom
         self._pend = torch.empty((B, C, self.sched.step + self.sched.lookahead, H, W), dtype=torch.float32, device=self._device)
-
-    def _setup_part(self):
-        m = self.model
-        m.use_overlap = self.use_overlap                # part of the chunk kinds' graph keys (_chunk_call)
-        if self.use_overlap:
-            m._overlap_offsets()
-        else:
-            m._set_cache_offset([m.decoder], 0)
 
     def _run(self, src, t0, t1, first, look):
         chunk = super()._run(src, t0, t1, first, look)
